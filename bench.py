@@ -14,6 +14,12 @@ all-reduce, global-norm clipping and the 8-bit AdamW update.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
 
 Rank 0 prints ONE JSON line (value = aggregate tokens/s over all ranks, max time over ranks).
+
+A plain run builds the model, warms up, times ``--steps`` steps and prints that line.  ``--full`` goes on to the
+sub-records, each a measurement of its own after the headline: the host launch time of one step
+(``host_launch_ms``), the reference-faithful config (``faithful``), the selective recompute policy
+(``selective_ckpt``) and, at world > 1, BASELINE config #4 on the ZeRO-3 engine (``zero3``).
+``--dump-outputs DIR`` writes what the last timed step computed (``dump_outputs``) for build-to-build comparison.
 """
 import argparse
 import contextlib
@@ -94,6 +100,28 @@ def build(args, device):
     return cfg, pm
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20   # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(path: str, loss, grad_norm, params) -> None:
+    """``--dump-outputs DIR``: what the last timed step handed back, as float32 ``DIR/<name>.npy`` — ``loss`` (the
+    step's return value), ``grad_norm`` (the global gradient norm its clipping used) and ``trainable_params``
+    (every trainable parameter after its optimizer update, flattened in ``parameters()`` order).  Past the byte
+    budget ``trainable_params`` is a fixed sample (seed 0, sorted indices), the same from run to run.  Weights,
+    batches and dropout keys are seeded, so two runs see identical inputs; on the GPU their results still differ
+    slightly (floating-point atomics in the backward, then the 8-bit optimizer state)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = torch.cat([p.detach().reshape(-1).float().cpu() for p in params])
+    keep = (DUMP_BUDGET_BYTES - 4096) // 4
+    if flat.numel() > keep:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        flat = flat[idx]
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "grad_norm.npy"), torch.as_tensor(grad_norm).detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "trainable_params.npy"), flat.numpy())
+
+
 def zero3_subrecord(args, device, rank: int, world: int, sync, beat=lambda: None) -> dict:
     """BASELINE config #4 at world > 1: ``Fine-Tuning/qwen3-14b-qlora-dist-deepspeed.py:164`` + ``ds_zero3_config.json``
     — the QLoRA model (--zero3-model, Qwen3-14B by default) on the ZeRO-3 engine, the client paged 8-bit AdamW on
@@ -164,6 +192,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the sub-records (host_launch_ms, faithful, selective_ckpt "
+                         "and, at world > 1, zero3: --host-steps / --faithful-steps / --selective-steps / --zero3-steps); "
+                         "without it the run ends with the headline's timed steps")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as float32 DIR/<name>.npy: loss, "
+                         "grad_norm, trainable_params (dump_outputs(); same arguments -> same inputs from run to run)")
     ap.add_argument("--model", default="qwen3-8b")
     ap.add_argument("--mode", default="qlora", choices=["qlora", "lora"])
     ap.add_argument("--micro-batch", type=int, default=2)
@@ -186,7 +221,7 @@ def main():
                     help="1: execute the grad-accum micro-batches in one pass (per-micro-batch loss "
                          "normalisation, identical gradient); 0: sequential micro-steps")
     ap.add_argument("--faithful-steps", type=int, default=5,
-                    help="after the headline timing, time this many steps of the reference-faithful config "
+                    help="--full: after the headline timing, time this many steps of the reference-faithful config "
                          "(gradient checkpointing on, sequential GA micro-steps) in the same process and report "
                          "them as the JSON's 'faithful' sub-record (0: skip; ddp strategy only)")
     ap.add_argument("--faithful-warmup", type=int, default=2)
@@ -202,19 +237,19 @@ def main():
                          "everywhere (no bf16 copy of the base: the memory-lean QLoRA step); expand = always expand "
                          "(default: LIPA_NF4_GEMM, else auto)")
     ap.add_argument("--zero3-steps", type=int, default=3,
-                    help="world > 1 (ddp strategy): after the headline, also time this many steps of BASELINE config #4 "
+                    help="--full, world > 1 (ddp strategy): after the headline, time this many steps of BASELINE config #4 "
                          "(--zero3-model QLoRA on the ZeRO-3 engine with configs/ds_zero3_config.json, same GA / optimizer) "
                          "as the 'zero3' sub-record, with its per-step collective record (0: skip)")
     ap.add_argument("--zero3-model", default=None,
                     help="model of the zero3 sub-record (default: qwen3-14b on GPUs, the headline model on CPU)")
     ap.add_argument("--selective-steps", type=int, default=3,
-                    help="after the faithful sub-record, time this many steps with the selective recompute policy "
+                    help="--full: after the faithful sub-record, time this many steps with the selective recompute policy "
                          "(GEMM outputs of the first forward kept, not recomputed) as the 'selective_ckpt' sub-record")
     ap.add_argument("--selective-reentrant", type=int, default=1,
                     help="the selective_ckpt sub-record's checkpoint form (1: reentrant, this framework's choice; the "
                          "faithful record follows --ckpt-reentrant, the reference's use_reentrant=False)")
     ap.add_argument("--host-steps", type=int, default=2,
-                    help="after the timed steps, issue this many steps onto an idle device and record the host "
+                    help="--full: after the timed steps, issue this many steps onto an idle device and record the host "
                          "launch time of one step (host_launch_ms; LIPA_HOST_PROFILE=<file> adds a cProfile of them)")
     ap.add_argument("--stall-timeout-s", type=float, default=900.0,
                     help="watchdog (utils/watchdog.py): no progress (model built, one step finished) for this long "
@@ -347,6 +382,11 @@ def main():
     wd.disarm()
     D.COMM.enabled = False
     comm = D.COMM.summary() if world > 1 else None
+    if args.dump_outputs:           # the last timed step's results (rank 0 writes; ZeRO-3 gathers its partitions first)
+        with (engine.gathered_params() if engine is not None else contextlib.nullcontext()):
+            if D.is_main():
+                dump_outputs(args.dump_outputs, loss, engine.last_grad_norm if engine is not None else opt.norm_out[0],
+                             [p for p in model.parameters() if p.requires_grad])
     gemm_forms = {k: round(v / max(1, args.steps), 2) for k, v in sorted(_lin.GEMM_STATS.items())}
     ms = 1000 * elapsed / max(1, args.steps)
     tokens = args.micro_batch * args.seq_len * args.grad_accum * world * args.steps
@@ -544,6 +584,15 @@ def main():
                 "checkpoint_policy": policy,
                 "micro_batch": args.micro_batch, "grad_accum": args.grad_accum, "peak_hbm_gib": round(fmem, 1)}
 
+    if not args.full:               # a plain run: the headline only (the sub-records take runs of their own)
+        if world > 1 and engine is None:
+            rec["zero3"] = {"skipped": "sub-records run with --full"}
+        gcm.__exit__(None, None, None)
+        emit()
+        wd.arm(120.0, "shutdown", exit_code=0)
+        D.destroy()
+        wd.disarm()
+        return
     if args.host_steps > 0:
         sub("host_launch_ms", host_record)
     if engine is None and not (args.grad_ckpt and not args.ga_fusion):

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/envab_$TAG
 mkdir -p $OUT
 for r in $(seq 1 ${ROUNDS:-2}); do
   for e in "$@"; do
-    env $e timeout -k 10 300 python3 $R/bench.py ${BENCH_ARGS:-} > $OUT/one.json 2> $OUT/one.err || { echo "[$e] failed"; tail -20 $OUT/one.err; exit 1; }
+    env $e timeout -k 10 300 python3 $R/bench.py --full ${BENCH_ARGS:-} > $OUT/one.json 2> $OUT/one.err || { echo "[$e] failed"; tail -20 $OUT/one.err; exit 1; }
     echo "round $r [$e] $(grep -o '"ms_per_step": [0-9.]*' $OUT/one.json | head -1) $(grep -o '"faithful": {[^}]*' $OUT/one.json | grep -o '"ms_per_step": [0-9.]*' | head -1)" | tee -a $OUT/ab.txt
   done
 done

@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest ${TESTS:-tests/test_trainer_gpu.py tests/t
 rc=$?; tail -3 $O/tests.txt; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
 rc=$?; tail -1 $O/smoke.txt; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err
 rc=$?; tail -1 $O/bench.json; grep "\[bench\]" $O/bench.err; [ $rc -eq 0 ] || exit $rc
 [ "${PROF:-1}" = 1 ] && bash scripts/gpu_step_prof.sh r5$TAG
 exit 0

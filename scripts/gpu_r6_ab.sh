@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 NAME=$1; N=${2:-3}
 O=$R/gpurun_out/ab_$NAME; mkdir -p $O
-ARGS="--steps ${STEPS:-20} --warmup 3 --faithful-steps ${FSTEPS:-0} --selective-steps 0 --host-steps 0"
+ARGS="--steps ${STEPS:-20} --warmup 3 ${FSTEPS:+--full} --faithful-steps ${FSTEPS:-0} --selective-steps 0 --host-steps 0"
 for i in $(seq 1 $N); do
   for v in tree $NAME; do
     if [ $v = tree ]; then B=$R/bench.py; else B=$R/ab_variants/$NAME/bench.py; fi

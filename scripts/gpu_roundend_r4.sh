@@ -9,5 +9,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 rc=$?; tail -4 $OUT/tests.txt; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1
 rc=$?; tail -2 $OUT/smoke.txt; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; tail -1 $OUT/bench.json; exit $rc

@@ -13,7 +13,7 @@ t1=$(date +%s)
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1
 rc=$?; tail -2 $OUT/smoke.txt; [ $rc -eq 0 ] || exit $rc
 t2=$(date +%s)
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; tail -1 $OUT/bench.json; grep "\[bench\]" $OUT/bench.err
 t3=$(date +%s)
 echo "seconds: tests $((t1-t0)) smoke $((t2-t1)) bench $((t3-t2))" | tee $OUT/times.txt

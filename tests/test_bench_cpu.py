@@ -34,11 +34,57 @@ def test_bench_self_launches_n_ranks():
     assert d["config"]["parallelism"] == "dp2"
 
 
+def _plain(tmp, *extra):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["OMP_NUM_THREADS"] = "2"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--model", "qwen3-tiny", "--seq-len", "64", "--dump-outputs", str(tmp), *extra]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0]), r.stderr
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """a plain run: the result line with its headline fields and no sub-record measured (those wait for --full);
+    --steps sets the timed steps; --dump-outputs writes the last timed step's results as float32 .npy, the same
+    from run to run (seeded weights, batches and dropout keys)."""
+    import numpy as np
+    d, err = _plain(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 * 64 * 2 / (d["ms_per_step"] / 1000)) / d["value"] < 0.02
+    assert d["host_launch_ms"] is None and "faithful" not in d and "selective_ckpt" not in d
+    assert "host launch time" not in err and "grad ckpt" not in err
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "grad_norm", "trainable_params")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["grad_norm.npy", "loss.npy", "trainable_params.npy"]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    last = [float(x) for x in __import__("re").findall(r"loss=([0-9.]+)", err)][-1]   # the timed steps' last loss
+    assert abs(float(a["loss"][0]) - last) < 1e-3 and a["grad_norm"][0] > 0
+    assert a["trainable_params"].size > 0 and np.abs(a["trainable_params"]).max() > 0
+    _plain(tmp_path / "b")
+    for n, v in a.items():
+        np.testing.assert_allclose(np.load(tmp_path / "b" / f"{n}.npy"), v, rtol=1e-5, atol=1e-7)
+
+
+def test_bench_full_run_measures_the_subrecords(tmp_path):
+    d, err = _plain(tmp_path / "f", "--full", "--faithful-steps", "1", "--faithful-warmup", "1",
+                    "--selective-steps", "1", "--host-steps", "1")
+    assert d["steps"] == 3 and d["host_launch_ms"] > 0
+    for k in ("faithful", "selective_ckpt"):
+        assert d[k]["value"] > 0 and d[k]["ms_per_step"] > 0 and d[k]["steps"] == 1, d[k]
+    assert os.path.exists(tmp_path / "f" / "loss.npy")
+
+
 @pytest.mark.parametrize("extra", [[], ["--ga-fusion", "0"], ["--strategy", "zero3"]])
 def test_bench_json_contract_two_ranks(extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--model", "qwen3-tiny", "--seq-len", "64", *extra]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--model", "qwen3-tiny", "--seq-len", "64", "--full",
+           *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, OMP_NUM_THREADS="2"))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -88,7 +134,7 @@ def test_bench_zero3_subrecord_four_ranks():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "4", "--steps", "1", "--warmup", "1", "--model", "qwen3-tiny", "--seq-len", "64",
-           "--faithful-steps", "0", "--selective-steps", "0", "--zero3-steps", "1"]
+           "--full", "--faithful-steps", "0", "--selective-steps", "0", "--zero3-steps", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -136,7 +182,7 @@ def _bench_with_fault(world, fault, extra=(), hang_s=None, timeout=600):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--steps", "1", "--warmup", "1", "--model", "qwen3-tiny", "--seq-len", "64",
-           "--host-steps", "1", "--zero3-steps", "2", *extra]
+           "--full", "--host-steps", "1", "--zero3-steps", "2", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -17,7 +17,7 @@ def test_bench_two_ranks_share_one_gpu(strategy):
     env = dict(os.environ, LIPA_DIST_BACKEND="gloo", LIPA_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0",
                PYTHONPATH=ROOT)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "qwen3-small",
-                          "--steps", "2", "--warmup", "1", "--strategy", strategy, "--faithful-steps", "1",
+                          "--steps", "2", "--warmup", "1", "--strategy", strategy, "--full", "--faithful-steps", "1",
                           "--selective-steps", "1", "--zero3-model", "qwen3-small", "--zero3-steps", "1"],
                          env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-3000:]

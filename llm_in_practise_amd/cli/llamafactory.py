@@ -10,7 +10,8 @@ YAML folds it into one plain scalar ``"a - b - c"``, which the loader splits bac
 intended list (and a line parser takes over for YAML that does not parse at all), so the shipped
 recipe runs as written.  Unsupported keys are reported, not silently
 applied (``packing``, ``enable_thinking``, ``flash_attn`` are accepted no-ops: attention is
-always the fused gfx950 kernel).
+always the fused gfx950 kernel).  ``neat_packing: true`` packs several samples into each
+``cutoff_len`` row with attention blocked between them (``cu_seqlens``, the varlen kernels).
 """
 from __future__ import annotations
 
@@ -95,7 +96,8 @@ def lf_train(cfg: dict, tokenizer: str | None = None):
     from ..models.qwen3 import Qwen3ForCausalLM, qwen3_config
     from ..parallel import dist as D
     from ..peft.lora import LoraConfig, get_peft_model, prepare_model_for_kbit_training, quantize_model_nf4
-    from ..train.data import DEEPSEEK_R1_SYSTEM, QWEN3_SYSTEM, SFTDataset, load_tokenizer
+    from ..train.data import (DEEPSEEK_R1_SYSTEM, QWEN3_SYSTEM, PackedDataCollator, PackedSFTDataset, SFTDataset,
+                              load_tokenizer)
     from ..train.trainer import Trainer, TrainingArguments
     unknown = sorted(k for k in cfg if k not in LF_IGNORED and k not in LF_KEYS)
     if unknown:
@@ -135,8 +137,16 @@ def lf_train(cfg: dict, tokenizer: str | None = None):
     recs = resolve_datasets(cfg.get("dataset"), cfg.get("dataset_dir", "data"))
     if cfg.get("max_samples"):
         recs = recs[:int(cfg["max_samples"])]
-    ds = SFTDataset(recs, tok, int(cfg.get("cutoff_len", 2048)), padding="longest", label_mode="assistant",
-                    system=system)
+    collator = None
+    if cfg.get("neat_packing"):   # several samples per row, attention blocked between them (cu_seqlens)
+        ds = PackedSFTDataset(recs, tok, int(cfg.get("cutoff_len", 2048)), label_mode="assistant", system=system)
+        collator = PackedDataCollator()
+        if D.is_main():
+            print(f"[lipa lf] neat_packing: {ds.num_samples} samples ({ds.num_tokens} tokens) -> {len(ds)} rows of "
+                  f"{int(cfg.get('cutoff_len', 2048))}", file=sys.stderr)
+    else:
+        ds = SFTDataset(recs, tok, int(cfg.get("cutoff_len", 2048)), padding="longest", label_mode="assistant",
+                        system=system)
     args = TrainingArguments(
         output_dir=cfg.get("output_dir", "finetuned/lf"),
         per_device_train_batch_size=int(cfg.get("per_device_train_batch_size", 1)),
@@ -149,8 +159,9 @@ def lf_train(cfg: dict, tokenizer: str | None = None):
         optim=cfg.get("optim", "adamw_torch"), report_to=[], remove_unused_columns=False,
         gradient_checkpointing=bool(cfg.get("gradient_checkpointing", False)),
         deepspeed=cfg.get("deepspeed"), seed=int(cfg.get("seed", 42)))
-    tr = Trainer(model, args, train_dataset=ds, tokenizer=tok)
+    tr = Trainer(model, args, train_dataset=ds, data_collator=collator, tokenizer=tok)
     out = tr.train()
+    out.metrics["train_rows"] = len(ds)
     tr.save_model(args.output_dir)
     tr.save_metrics("train", out.metrics)
     tr.save_state()
@@ -162,7 +173,7 @@ LF_KEYS = {"model_name_or_path", "stage", "finetuning_type", "lora_target", "lor
            "logging_steps", "save_steps", "per_device_train_batch_size", "gradient_accumulation_steps",
            "learning_rate", "num_train_epochs", "max_steps", "lr_scheduler_type", "warmup_ratio", "warmup_steps",
            "bf16", "fp16", "optim", "gradient_checkpointing", "deepspeed", "seed", "rope_scaling",
-           "adapter_name_or_path", "export_dir"}
+           "adapter_name_or_path", "export_dir", "neat_packing"}
 
 
 def lf_export(cfg: dict, tokenizer: str | None = None):

@@ -191,8 +191,8 @@ def cmd_finetune(a):
     from ..cli.recipes import PRESETS
     from ..parallel import dist as D
     from ..peft.lora import LoraConfig, get_peft_model, prepare_model_for_kbit_training
-    from ..train.data import (ByteTokenizer, DataCollatorForLanguageModeling, SFTDataset, SyntheticLMDataset,
-                              load_records, load_tokenizer, synthetic_self_cognition)
+    from ..train.data import (ByteTokenizer, DataCollatorForLanguageModeling, PackedDataCollator, PackedSFTDataset,
+                              SFTDataset, SyntheticLMDataset, load_records, load_tokenizer, synthetic_self_cognition)
     from ..train.trainer import Trainer, TrainingArguments
     p = PRESETS[a.preset]
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -215,9 +215,17 @@ def cmd_finetune(a):
         else None
     if tok is not None:
         recs = load_records(a.data) if a.data else synthetic_self_cognition()
-        train_ds = SFTDataset(recs, tok, p.max_length, p.padding, label_mode=a.label_mode, system=p.system,
-                              space_before_end=p.space_before_end)
-        collator = DataCollatorForLanguageModeling(tok, mlm=False) if a.label_mode == "reference" else None
+        if a.packing:   # neat packing: several samples per max_length row, attention blocked between them
+            train_ds = PackedSFTDataset(recs, tok, p.max_length, label_mode=a.label_mode, system=p.system,
+                                        space_before_end=p.space_before_end)
+            collator = PackedDataCollator()
+            if D.is_main():
+                print(f"packing: {train_ds.num_samples} samples ({train_ds.num_tokens} tokens) -> {len(train_ds)} "
+                      f"rows of {p.max_length}", file=sys.stderr)
+        else:
+            train_ds = SFTDataset(recs, tok, p.max_length, p.padding, label_mode=a.label_mode, system=p.system,
+                                  space_before_end=p.space_before_end)
+            collator = DataCollatorForLanguageModeling(tok, mlm=False) if a.label_mode == "reference" else None
     else:                                        # no tokenizer available offline: synthetic ids at the preset shape
         vocab = model.config.vocab_size
         train_ds = SyntheticLMDataset(vocab, p.max_length, a.synthetic_samples)
@@ -912,6 +920,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--epochs", type=float, default=None)
     p.add_argument("--max-steps", dest="max_steps", type=int, default=-1)
     p.add_argument("--label-mode", dest="label_mode", default="reference", choices=["reference", "assistant", "none"])
+    p.add_argument("--packing", action="store_true",
+                   help="neat sample packing: several samples per row, attention blocked between them (default off)")
     p.add_argument("--no-grad-ckpt", dest="no_grad_ckpt", action="store_true")
     p.add_argument("--no-deepspeed", dest="no_deepspeed", action="store_true")
     p.add_argument("--resume", default=None)

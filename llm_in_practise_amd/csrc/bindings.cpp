@@ -76,6 +76,10 @@ void launch_attn_bwd(const void*, const void*, const void*, const void*, const v
                      int, int, void*, void*, void*, float*, int, int, int, int, int, int, float, float, uint64_t,
                      float*, hipStream_t);
 int attn_dkv_nsplit(int, int, int, int);
+void launch_attn_varlen_fwd(const void*, const void*, const void*, int, int, int, const int*, void*, float*, int, int,
+                            int, int, int, float, hipStream_t);
+void launch_attn_varlen_bwd(const void*, const void*, const void*, const void*, const void*, const float*, const int*,
+                            int, int, int, void*, void*, void*, float*, int, int, int, int, int, float, hipStream_t);
 void attn_set_trace(void*);
 
 void launch_gemv_w4(int, const void*, int, const uint8_t*, const float*, const float*, int, const void*, void*, int, int,
@@ -1001,6 +1005,59 @@ std::vector<Tensor> attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o
   return {dq, dk, dv};
 }
 
+// Packed (varlen) causal attention: q [T, hq*d], k/v [T, hkv*d] (strided views allowed), sequence b = rows
+// cu_seqlens[b] .. cu_seqlens[b+1] - 1 (int32 [N+1] on the device; cu_seqlens[0] == 0 and cu_seqlens[N] == T are the
+// caller's to check, it holds the host copy).  lse is [N, hq, max_seqlen rounded up to 64], internal to the op.
+static int64_t attn_varlen_check(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu, int64_t max_seqlen,
+                                 int64_t hq, int64_t hkv, int64_t d, const char* who) {
+  TORCH_CHECK(d == 32 || d == 64 || d == 96 || d == 128, who, ": head_dim in {32, 64, 96, 128}");
+  TORCH_CHECK(hkv > 0 && hq % hkv == 0, who, ": GQA group");
+  TORCH_CHECK(cu.is_cuda() && cu.scalar_type() == at::kInt && cu.dim() == 1 && cu.is_contiguous() && cu.numel() >= 2,
+              who, ": cu_seqlens must be a contiguous int32 [N+1] tensor on the device");
+  const int64_t T = q.size(0);
+  TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= T, who, ": max_seqlen in [1, T]");
+  attn_check(q, T, hq, d, "q");
+  attn_check(k, T, hkv, d, "k");
+  attn_check(v, T, hkv, d, "v");
+  return T;
+}
+
+std::vector<Tensor> attn_varlen_fwd(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens, int64_t max_seqlen, int64_t hq,
+                                    int64_t hkv, int64_t d, double scale, double p_drop) {
+  TORCH_CHECK(p_drop == 0.0, "attn_varlen_fwd: attention dropout is not supported with cu_seqlens");
+  const int64_t T = attn_varlen_check(q, k, v, cu_seqlens, max_seqlen, hq, hkv, d, "attn_varlen_fwd");
+  const int64_t N = cu_seqlens.numel() - 1, ss = (max_seqlen + 63) / 64 * 64;
+  auto o = at::empty({T, hq * d}, q.options());
+  auto lse = at::empty({N, hq, ss}, q.options().dtype(at::kFloat));
+  launch_attn_varlen_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                         cu_seqlens.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(), (int)N, (int)max_seqlen,
+                         (int)hq, (int)hkv, (int)d, (float)scale, stream());
+  return {o, lse};
+}
+
+std::vector<Tensor> attn_varlen_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor cu_seqlens,
+                                    int64_t max_seqlen, int64_t hq, int64_t hkv, int64_t d, double scale,
+                                    double p_drop) {
+  TORCH_CHECK(p_drop == 0.0, "attn_varlen_bwd: attention dropout is not supported with cu_seqlens");
+  const int64_t T = attn_varlen_check(q, k, v, cu_seqlens, max_seqlen, hq, hkv, d, "attn_varlen_bwd");
+  const int64_t N = cu_seqlens.numel() - 1, ss = (max_seqlen + 63) / 64 * 64;
+  attn_check(o, T, hq, d, "o");
+  attn_check(dout, T, hq, d, "dout");
+  TORCH_CHECK(dout.stride(0) == hq * d && o.stride(0) == hq * d, "attn_varlen_bwd: o / dout must be dense [T, hq*d]");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.dim() == 3 && lse.size(0) == N &&
+                  lse.size(1) == hq && lse.size(2) == ss,
+              "attn_varlen_bwd: lse must be the forward's [N, hq, max_seqlen rounded up to 64]");
+  auto dq = at::empty({T, hq * d}, q.options());
+  auto dk = at::empty({T, hkv * d}, q.options());
+  auto dv = at::empty({T, hkv * d}, q.options());
+  auto delta = at::empty({N, hq, ss}, q.options().dtype(at::kFloat));
+  launch_attn_varlen_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                         cu_seqlens.data_ptr<int>(), q.stride(0), k.stride(0), v.stride(0), dq.data_ptr(),
+                         dk.data_ptr(), dv.data_ptr(), delta.data_ptr<float>(), (int)N, (int)max_seqlen, (int)hq,
+                         (int)hkv, (int)d, (float)scale, stream());
+  return {dq, dk, dv};
+}
+
 // ------------------------------------------------------------------ fused LoRA branch kernels
 // out = scale·D(x)·Wᵀ over x[:, c0:c0+K] (row stride = x.stride(0)); writes bf16 into outb (a column
 // slice view, any row stride) and/or returns fp32 [M, r].
@@ -1726,6 +1783,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_fwd_ext", &attn_fwd_ext);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_varlen_fwd", &attn_varlen_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens"),
+        py::arg("max_seqlen"), py::arg("hq"), py::arg("hkv"), py::arg("d"), py::arg("scale"), py::arg("p_drop") = 0.0);
+  m.def("attn_varlen_bwd", &attn_varlen_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+        py::arg("lse"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("hq"), py::arg("hkv"), py::arg("d"),
+        py::arg("scale"), py::arg("p_drop") = 0.0);
   // debug: phase timestamps of the D = 128 dK/dV kernel go into `buf` (u8/i64 tensor) while set; None clears
   m.def("attn_set_trace", [](optional<Tensor> buf) { attn_set_trace(buf && buf->defined() ? buf->data_ptr() : nullptr); });
   m.def("car_alloc", &car_alloc_py);

@@ -56,6 +56,23 @@ def _stamp(path: str, flags: list[str], deps: list[str]) -> str:
     return h.hexdigest()[:16]
 
 
+def _local_includes(src: str) -> list[str]:
+    """The headers ``src`` pulls in with ``#include "..."`` (relative to its own directory), transitively."""
+    import re
+    seen: list[str] = []
+    todo = [src]
+    while todo:
+        cur = todo.pop()
+        with open(cur) as f:
+            names = re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
+        for n in names:
+            p = os.path.normpath(os.path.join(os.path.dirname(cur), n))
+            if os.path.exists(p) and p not in seen:
+                seen.append(p)
+                todo.append(p)
+    return sorted(seen)
+
+
 def _compile(src: str, flags: list[str], compiler: list[str], deps: list[str]) -> str:
     os.makedirs(BUILD, exist_ok=True)
     base = os.path.relpath(src, PKG).replace(os.sep, "_")
@@ -82,7 +99,8 @@ def build_hip_extension(jobs: int | None = None, verbose: bool = True) -> str:
     jobs = jobs or int(os.environ.get("MAX_JOBS", "8"))
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         futs = [ex.submit(_compile, s, kflags, [hipcc], headers) for s in srcs]
-        futs.append(ex.submit(_compile, os.path.join(HERE, "bindings.cpp"), bflags, ["g++"], []))
+        bsrc = os.path.join(HERE, "bindings.cpp")   # shares structs with the kernels through their headers
+        futs.append(ex.submit(_compile, bsrc, bflags, ["g++"], _local_includes(bsrc)))
         objs = [f.result() for f in futs]
     out = os.path.join(PKG, f"_C{EXT_SUFFIX}")
     link = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out + ".tmp"] + objs

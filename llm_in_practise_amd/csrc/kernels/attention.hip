@@ -118,7 +118,7 @@ static int attn_lpt() { return 1; }
 // q_offs[b] + i (0 without q_offs): chunked / prefix-cache suffix prefill is the same kernel with
 // the causal limit key ≤ q_off + i.  kv_lens[b] (optional) masks keys ≥ kv_lens[b] (right padding,
 // BERT key-padding masks, the filled part of a cache).
-template <int D, int PF, int QT>
+template <int D, int PF, int QT, bool VL = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_k(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                   const bf16* __restrict__ V, int ldq, int ldk, int ldv,
                                                   const int* __restrict__ kv_lens, const int* __restrict__ q_offs,
@@ -145,10 +145,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const bf16* __restrict__ Q,
   const int hk = h / (hq / hkv);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
   const int q0 = qb * QB + 16 * QT * w;
+  int sst = Sq, r0 = 0;                // lse row stride; VL: the sequence's first row
+  if constexpr (VL) {   // sequence b of a packed batch: rows cu[b] .. cu[b+1] - 1, Sq was max_seqlen up to here
+    r0 = kv_lens[b];
+    sst = (Sq + 63) & ~63;
+    Sq = Skv = kv_lens[b + 1] - r0;
+    kv_lens = nullptr;
+    if (qb * QB >= Sq) return;   // uniform: no query of this workgroup exists
+  }
   const int qoff = q_offs ? q_offs[b] : 0;
   const int kvlen = min(kv_lens ? kv_lens[b] : Skv, Skv);
-  const size_t tok0 = (size_t)b * Sq;          // query / output rows
-  const size_t ktok0 = (size_t)b * kv_rows;     // key / value rows
+  const size_t tok0 = VL ? (size_t)r0 : (size_t)b * Sq;            // query / output rows
+  const size_t ktok0 = VL ? (size_t)r0 : (size_t)b * kv_rows;      // key / value rows
 
   // Q fragments (B operand of Sᵀ = K·Qᵀ): Q[q0 + 16qt + li][32s + 8g + j]
   bf16x8 qf[QT][NS];
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const bf16* __restrict__ Q,
       *reinterpret_cast<bf16x4*>(O + (tok0 + q) * (size_t)(hq * D) + h * D + 16 * dt + 4 * g) = o;
     }
     if (g == 0)
-      lse[((size_t)b * hq + h) * Sq + q] =
+      lse[((size_t)b * hq + h) * sst + q] =
           l_run[qt] > 0.f ? (m_run[qt] * scale_log2 + log2f(l_run[qt])) * 0.6931471805599453f : INFINITY;
   }
 }
@@ -369,7 +377,7 @@ __device__ __forceinline__ void attn_dma16(const rsrc_t& rs, uint32_t m0v, uint3
       : "memory");
 }
 
-template <bool DROP>
+template <bool DROP, bool VL = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd128_k(const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                      const bf16* __restrict__ V, int ldq, int ldk, int ldv,
                                                      const int* __restrict__ kv_lens, const int* __restrict__ q_offs,
@@ -386,9 +394,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd128_k(const bf16* __restrict__
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r32 = lane & 31, hi = lane >> 5;
   const int q0w = qb * 128 + 32 * w;   // this wave's first query
   const int qa = q0w + r32;            // this lane's query
+  int sst = Sq, r0 = 0;                // lse row stride; VL: the sequence's first row
+  if constexpr (VL) {   // sequence b of a packed batch (scalar loads, ahead of every DMA): Sq was max_seqlen up to here
+    r0 = kv_lens[b];
+    sst = (Sq + 63) & ~63;
+    Sq = Skv = kv_lens[b + 1] - r0;
+    kv_lens = nullptr;
+    if (qb * 128 >= Sq) return;   // uniform: no query of this workgroup exists
+  }
   const int qoff = q_offs ? q_offs[b] : 0;
   const int kvlen = min(kv_lens ? kv_lens[b] : Skv, Skv);
-  const size_t tok0 = (size_t)b * Sq, ktok0 = (size_t)b * kv_rows;
+  const size_t tok0 = VL ? (size_t)r0 : (size_t)b * Sq, ktok0 = VL ? (size_t)r0 : (size_t)b * kv_rows;
 
   // Q as the B operand of Sᵀ = K·Qᵀ: lane (q, hi) holds Q[q][16ds + 8hi + j]
   bf16x8 qf[8];
@@ -557,7 +573,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd128_k(const bf16* __restrict__
             bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)c[0], (bf16)c[1], (bf16)c[2], (bf16)c[3]};
     }
   if (hi == 0 && qa < Sq)
-    lse[((size_t)b * hq + h) * Sq + qa] = lt > 0.f ? (m_run * scale_log2 + log2f(lt)) * 0.6931471805599453f : INFINITY;
+    lse[((size_t)b * hq + h) * sst + qa] = lt > 0.f ? (m_run * scale_log2 + log2f(lt)) * 0.6931471805599453f : INFINITY;
 }
 
 // ============================================================================ backward
@@ -570,7 +586,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd128_k(const bf16* __restrict__
 //    registers) that sweeps every q-head of its GQA group × 64-query tiles, so the group's
 //    dK/dV sum stays in registers: no fp32 partials, no finalize pass.  Q/dO tiles (plus
 //    their lse/delta) are register-prefetched one tile ahead into double-buffered LDS.
-template <int D, int PF>
+template <int D, int PF, bool VL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_k(const bf16* __restrict__ dO, const bf16* __restrict__ O,
                                                      const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                      const bf16* __restrict__ V, const float* __restrict__ lse,
@@ -589,15 +605,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_k(const bf16* __restrict__
   const int hk = h / (hq / hkv);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
   const int q0 = qb * 64;
+  int sst = S, r0 = 0;                 // lse / delta row stride; VL: the sequence's first row
+  if constexpr (VL) {   // sequence b of a packed batch: rows cu[b] .. cu[b+1] - 1, S was max_seqlen up to here
+    r0 = kv_lens[b];
+    sst = (S + 63) & ~63;
+    S = kv_lens[b + 1] - r0;
+    kv_lens = nullptr;
+    if (q0 >= S) return;   // uniform: no query of this workgroup exists
+  }
   const int qa = q0 + 16 * w + li;  // this lane's query (>= S in a tail tile: computed, never stored)
   const int qc = qa < S ? qa : S - 1;
   const int kvlen = min(kv_lens ? kv_lens[b] : S, S);
-  const size_t tok0 = (size_t)b * S;
+  const size_t tok0 = VL ? (size_t)r0 : (size_t)b * S;
   const size_t ldo = (size_t)hq * D;
 
   bf16x8 qf[NS], dof[NS];
   float dsum = 0.f;
-  const size_t bh = ((size_t)b * hq + h) * S;
+  const size_t bh = ((size_t)b * hq + h) * sst;
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     const size_t off = (tok0 + qc) * ldo + h * D + 32 * s + 8 * g;
@@ -725,7 +749,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_k(const bf16* __restrict__
 // (row reads of the swizzled K / V images), dS = P∘(dP − delta) in registers, dQᵀ += Kᵀ·dSᵀ with Kᵀ from the
 // transposed reads of the same K image and dS as the B operand in accumulator-row slot order (no lane
 // movement).  Writes delta for the dK/dV kernel, as attn_bwd_dq_k.
-template <bool DROP>
+template <bool DROP, bool VL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq128_k(const bf16* __restrict__ dO, const bf16* __restrict__ O,
                                                         const bf16* __restrict__ Q, const bf16* __restrict__ K,
                                                         const bf16* __restrict__ V, const float* __restrict__ lse,
@@ -741,10 +765,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq128_k(const bf16* __restric
   const int qb = nqb - 1 - i0;
   const int hk = h / (hq / hkv);
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r32 = lane & 31, hi = lane >> 5;
+  int sst = S, r0 = 0;                 // lse / delta row stride; VL: the sequence's first row
+  if constexpr (VL) {   // sequence b of a packed batch (scalar loads, ahead of every DMA): S was max_seqlen up to here
+    r0 = kv_lens[b];
+    sst = (S + 63) & ~63;
+    S = kv_lens[b + 1] - r0;
+    kv_lens = nullptr;
+    if (qb * 128 >= S) return;   // uniform: no query of this workgroup exists
+  }
   const int q0w = qb * 128 + 32 * w, qa = q0w + r32, qc = qa < S ? qa : S - 1;
   const int kvlen = min(kv_lens ? kv_lens[b] : S, S);
-  const size_t tok0 = (size_t)b * S, ldo = (size_t)hq * D;
-  const size_t bh = ((size_t)b * hq + h) * S;
+  const size_t tok0 = VL ? (size_t)r0 : (size_t)b * S, ldo = (size_t)hq * D;
+  const size_t bh = ((size_t)b * hq + h) * sst;
 
   bf16x8 qf[8], dof[8];
   float dsum = 0.f;
@@ -886,7 +918,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq128_k(const bf16* __restric
 // as B operands in accumulator-row slot order.  The four waves of a key half meet in LDS at the end.
 // Split key blocks (nsplit) write fp32 partials as attn_bwd_dkv_k.  160 KB LDS, ≤ 256 VGPRs.
 // Requires ldq % 128 == 0 (row strides in whole 256-B units: see attn_dkv128_ok).
-template <bool DROP, bool TRACE = false>
+template <bool DROP, bool TRACE = false, bool VL = false>
 __global__ __launch_bounds__(512, 1) void attn_bwd_dkv128_k(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                                                          const bf16* __restrict__ K, const bf16* __restrict__ V,
                                                          const float* __restrict__ lse,
@@ -913,8 +945,18 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkv128_k(const bf16* __restri
   const int kw2 = w & 1, qh = (w >> 1) & 1, hw = w >> 2, w4 = w & 3;
   const int kb0 = kbi * 64;
   const int kw = kb0 + 32 * kw2 + r32;   // this lane's key
+  size_t tok0 = (size_t)b * S;
+  int sst = S;                           // lse / delta row stride
+  if constexpr (VL) {   // sequence b of a packed batch (scalar loads, ahead of every DMA): S was max_seqlen up to here
+    const int c0 = kv_lens[b];
+    tok0 = (size_t)c0;
+    sst = (S + 63) & ~63;
+    S = kv_lens[b + 1] - c0;
+    kv_lens = nullptr;
+    if (kb0 >= S) return;   // uniform: no key of this workgroup exists
+  }
   const int kvlen = min(kv_lens ? kv_lens[b] : S, S);
-  const size_t tok0 = (size_t)b * S, ldo = (size_t)hq * D, ldkv = (size_t)hkv * D;
+  const size_t ldo = (size_t)hq * D, ldkv = (size_t)hkv * D;
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr_t)smem);
 
   // K / V images of the 64 keys (512 threads × 2 chunks each per tensor)
@@ -1011,7 +1053,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkv128_k(const bf16* __restri
     if (!act_of(it2)) return;
     const int j2 = hw + 2 * (it2 / nqt);
     const int qb = (qt0 + it2 % nqt) * 64;
-    const size_t bh = ((size_t)b * hq + hk * rep + j2) * S + qb;
+    const size_t bh = ((size_t)b * hq + hk * rep + j2) * sst + qb;
     const rsrc_t rl = attn_rsrc(lse + bh, (size_t)(S - qb) * 4);
     const rsrc_t rd = attn_rsrc(delta + bh, (size_t)(S - qb) * 4);
 #pragma unroll
@@ -1170,7 +1212,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkv128_k(const bf16* __restri
 
 // HALVES = 2: a 512-thread workgroup, the two 4-wave halves sweep different q-heads of the GQA
 // group over the SAME 64 keys (2 waves per SIMD instead of 1) and meet in LDS at the end.
-template <int D, int HALVES, int PF>
+template <int D, int HALVES, int PF, bool VL = false>
 __global__ __launch_bounds__(256 * HALVES) void attn_bwd_dkv_k(const bf16* __restrict__ dO, const bf16* __restrict__ Q,
                                                       const bf16* __restrict__ K, const bf16* __restrict__ V,
                                                       const float* __restrict__ lse, const float* __restrict__ delta,
@@ -1205,9 +1247,18 @@ __global__ __launch_bounds__(256 * HALVES) void attn_bwd_dkv_k(const bf16* __res
   const int w = tid >> 6, lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
   const int kb0 = kbi * 64;
   const int kw = kb0 + 16 * w + li;  // this lane's key (column of the S / dP tiles)
+  size_t tok0 = (size_t)b * S;
+  int sst = S;                       // lse / delta row stride
+  if constexpr (VL) {   // sequence b of a packed batch: rows cu[b] .. cu[b+1] - 1, S was max_seqlen up to here
+    const int c0 = kv_lens[b];
+    tok0 = (size_t)c0;
+    sst = (S + 63) & ~63;
+    S = kv_lens[b + 1] - c0;
+    kv_lens = nullptr;
+    if (kb0 >= S) return;   // uniform: no key of this workgroup exists
+  }
   const int kwc = kw < S ? kw : S - 1;
   const int kvlen = min(kv_lens ? kv_lens[b] : S, S);
-  const size_t tok0 = (size_t)b * S;
   const size_t ldo = (size_t)hq * D, ldkv = (size_t)hkv * D;
 
   bf16x8 kf[NS], vf[NS];
@@ -1248,7 +1299,7 @@ __global__ __launch_bounds__(256 * HALVES) void attn_bwd_dkv_k(const bf16* __res
       dr[set][p] = *reinterpret_cast<const bf16x8*>(dO + tq * ldo + h * D + ch * 8);
     }
     if (tid < 128) {
-      const size_t bh = ((size_t)b * hq + h) * S + min(qa0 + (tid & 63), S - 1);
+      const size_t bh = ((size_t)b * hq + h) * sst + min(qa0 + (tid & 63), S - 1);
       st[set] = tid < 64 ? lse[bh] * LOG2E : delta[bh];
     }
   };
@@ -1531,6 +1582,75 @@ void launch_attn_bwd(const void* dout, const void* q, const void* k, const void*
     const int ldkv = hkv * D, rows = std::min(nsplit * 64, S);
     const size_t n4 = (size_t)B * rows * ldkv / 4;
     attn_dkv_fin_k<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(ws, (bf16*)dk, (bf16*)dv, B, S, ldkv, rows, scale);
+  }
+  LIPA_CHECK_LAUNCH();
+}
+
+// ============================================================================ packed (varlen) batches
+// The FlashAttention-varlen contract: tokens of N sequences packed back to back as [T, H·D], sequence b = rows
+// cu_seqlens[b] .. cu_seqlens[b+1] - 1 (int32, device), max_seqlen on the host sizes the block axis.  The same
+// kernel bodies (VL = true) with cu_seqlens in the kv_lens slot and max_seqlen as S: the grid's batch axis is
+// the sequence, every bound is the sequence's own length, a workgroup past its sequence's end returns at once.
+// Causal, no dropout, no q_offs / kv_lens, key blocks never split.  lse / delta are [N, hq, sstride], sstride =
+// max_seqlen rounded up to 64 (the kernels derive it from S): the dK/dV kernel's 16-B lse / delta loads stay
+// aligned whatever cu_seqlens holds.
+void launch_attn_varlen_fwd(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                            const int* cu_seqlens, void* o, float* lse, int N, int max_seqlen, int hq, int hkv,
+                            int D, float scale, hipStream_t st) {
+  const DropParams dp = make_drop(0.f, 0);
+  dim3 grid((max_seqlen + 127) / 128, hq, N), blk(256);
+  const float sl2 = scale * LOG2E;
+  const int causal = 1 | (attn_lpt() << 1);
+  if (D == 128) {
+    attn_fwd128_k<false, true><<<grid, blk, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, ldq, ldk, ldv,
+                                                     cu_seqlens, nullptr, (bf16*)o, lse, max_seqlen, max_seqlen,
+                                                     max_seqlen, hq, hkv, causal, sl2, dp);
+  } else {
+#define FWD(PFV, QTV)                                                                                           \
+  attn_fwd_k<DD, PFV, QTV, true><<<grid, blk, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, ldq, ldk, \
+                                                       ldv, cu_seqlens, nullptr, (bf16*)o, lse, max_seqlen,      \
+                                                       max_seqlen, max_seqlen, hq, hkv, causal, sl2, dp)
+    LIPA_ATTN_D3(D, FWD(1, 2));
+#undef FWD
+  }
+  LIPA_CHECK_LAUNCH();
+}
+
+void launch_attn_varlen_bwd(const void* dout, const void* q, const void* k, const void* v, const void* o,
+                            const float* lse, const int* cu_seqlens, int ldq, int ldk, int ldv, void* dq, void* dk,
+                            void* dv, float* delta, int N, int max_seqlen, int hq, int hkv, int D, float scale,
+                            hipStream_t st) {
+  const float sl2 = scale * LOG2E;
+  const DropParams dp = make_drop(0.f, 0);
+  const int nb = (max_seqlen + 63) / 64;
+  const int causal = 1 | (attn_lpt() << 1);
+  dim3 gkv(nb, hkv, N), blk(256);
+  // dQ first (it writes delta), then dK/dV
+  if (D == 128) {
+    dim3 gq((max_seqlen + 127) / 128, hq, N);
+    attn_bwd_dq128_k<false, true><<<gq, blk, 0, st>>>((const bf16*)dout, (const bf16*)o, (const bf16*)q,
+                                                      (const bf16*)k, (const bf16*)v, lse, delta, cu_seqlens, ldq,
+                                                      ldk, ldv, (bf16*)dq, max_seqlen, hq, hkv, causal, scale, sl2,
+                                                      dp);
+    attn_bwd_dkv128_k<false, false, true><<<gkv, 512, 0, st>>>((const bf16*)dout, (const bf16*)q, (const bf16*)k,
+                                                               (const bf16*)v, lse, delta, cu_seqlens, ldq, ldk,
+                                                               ldv, (bf16*)dk, (bf16*)dv, max_seqlen, hq, hkv, 1,
+                                                               scale, sl2, dp, nullptr, 0);
+  } else {
+    dim3 gq(nb, hq, N);
+#define DKV(DD, HV)                                                                                               \
+  attn_bwd_dkv_k<DD, HV, 1, true><<<gkv, 256 * HV, 0, st>>>((const bf16*)dout, (const bf16*)q, (const bf16*)k,     \
+                                                            (const bf16*)v, lse, delta, cu_seqlens, ldq, ldk,     \
+                                                            ldv, (bf16*)dk, (bf16*)dv, max_seqlen, hq, hkv, 1,    \
+                                                            scale, sl2, dp, nullptr, 0)
+#define RUN(DD)                                                                                                   \
+  attn_bwd_dq_k<DD, 2, true><<<gq, blk, 0, st>>>((const bf16*)dout, (const bf16*)o, (const bf16*)q, (const bf16*)k, \
+                                                 (const bf16*)v, lse, delta, cu_seqlens, ldq, ldk, ldv, (bf16*)dq, \
+                                                 max_seqlen, hq, hkv, causal, scale, sl2, dp);                    \
+  if ((hq / hkv) % 2 == 0) DKV(DD, 2); else DKV(DD, 1)
+    LIPA_ATTN_D3(D, RUN(DD));
+#undef RUN
+#undef DKV
   }
   LIPA_CHECK_LAUNCH();
 }

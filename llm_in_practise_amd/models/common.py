@@ -6,6 +6,7 @@ import dataclasses
 import torch
 import torch.nn as nn
 
+from ..ops.attention import flash_attention_varlen, native_ok
 from ..ops.linear import LoraBranch, fused_linear
 from ..peft.lora import Linear4bit, LoraLayer, base_of
 from ..quant.int4 import Int4Linear, Int4Weight, int4_linear
@@ -185,9 +186,10 @@ class PackedPrefill:
     into their KV-cache slots (the serving engine's admission path).
 
     Every token-wise op (projections, norms, SwiGLU: nearly all prefill FLOPs) runs on the
-    packed tokens only; attention scatters q/k/v into a right-padded ``[B, S]`` view for the
-    flash kernel (causal, per-row ``kv_lens``) and gathers the valid rows back, and each
-    layer's K/V rows are written into the cache slots with one indexed copy.  Against padding
+    packed tokens only; attention runs the varlen flash kernel on the packed q/k/v directly
+    (``cu_seqlens`` = the prompts' boundaries; off the HIP path: scatter into a right-padded
+    ``[B, S]`` view, per-row ``kv_lens``, gather back), and each layer's K/V rows are written
+    into the cache slots with one indexed copy.  Against padding
     every prompt to the longest one this removes the padded GEMM work (≈ 40 % on chat-length
     prompts) and the scratch-cache → slot copy."""
 
@@ -202,12 +204,16 @@ class PackedPrefill:
         self.cache_idx = (sl[tb] * cache.max_len + tp).to(device)
         self.kv_lens = torch.tensor(lens, dtype=torch.int32, device=device)
         self.last = (torch.cumsum(torch.tensor(lens), 0) - 1).to(device)
+        self.cu_host = [0] + torch.cumsum(torch.tensor(lens), 0).tolist()
+        self.cu_seqlens = torch.tensor(self.cu_host, dtype=torch.int32, device=device)
 
     def attend(self, layer: int, q, k, v, hq: int, hkv: int, d: int, attention_fn):
         self.cache.k[layer].view(-1, hkv * d).index_copy_(0, self.cache_idx, k)
         self.cache.v[layer].view(-1, hkv * d).index_copy_(0, self.cache_idx, v)
         if self.B == 1:
             return attention_fn(q, k, v, 1, self.S, hq, hkv, d, causal=True, kv_lens=None)
+        if native_ok(q, d):
+            return flash_attention_varlen(q, k, v, self.cu_seqlens, self.S, hq, hkv, d, cu_host=self.cu_host)
         n = self.B * self.S
 
         def pad(t):

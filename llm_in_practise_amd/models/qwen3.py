@@ -27,7 +27,7 @@ import torch.nn as nn
 from ..ops import reference as ref
 from ..ops.activation import swiglu_fused
 from ..ops.mlp import fusable as mlp_fusable, swiglu_mlp
-from ..ops.attention import flash_attention, flash_attention_prefix
+from ..ops.attention import check_cu_seqlens, flash_attention, flash_attention_prefix, flash_attention_varlen
 from ..ops.decode import decode_attention_append
 from ..ops.linear import checkpoint as lora_checkpoint
 from ..ops.loss import fused_linear_cross_entropy, shift_labels
@@ -143,6 +143,29 @@ def qwen3_config(name: str, **overrides) -> Qwen3Config:
     return Qwen3Config(**kw)
 
 
+def _packing_kwargs(cu_seqlens, max_seqlen, cu_q, cu_k, max_q, max_k):
+    """Fold HF's padding-free kwargs into (cu_seqlens, max_seqlen); self-attention only, so q and k forms must agree."""
+    def same(a, b):
+        if isinstance(a, torch.Tensor) or isinstance(b, torch.Tensor):
+            a, b = torch.as_tensor(a), torch.as_tensor(b)
+            return a.shape == b.shape and bool((a.cpu() == b.cpu()).all())
+        return a == b
+    for a, b, what in ((cu_q, cu_k, "cu_seq_lens_q / cu_seq_lens_k"), (max_q, max_k, "max_length_q / max_length_k")):
+        if (a is None) != (b is None) or (a is not None and not same(a, b)):
+            raise ValueError(f"{what} must both be given and equal (self-attention over one packed batch)")
+    if cu_q is not None:
+        if cu_seqlens is not None and not same(cu_seqlens, cu_q):
+            raise ValueError("cu_seqlens and cu_seq_lens_q differ")
+        cu_seqlens = cu_q
+    if max_q is not None:
+        if max_seqlen is not None and int(max_seqlen) != int(max_q):
+            raise ValueError("max_seqlen and max_length_q differ")
+        max_seqlen = int(max_q)
+    if cu_seqlens is None and max_seqlen is not None:
+        raise ValueError("max_seqlen without cu_seqlens")
+    return cu_seqlens, max_seqlen
+
+
 class Qwen3Attention(nn.Module):
     def __init__(self, cfg: Qwen3Config, layer_idx: int):
         super().__init__()
@@ -167,7 +190,7 @@ class Qwen3Attention(nn.Module):
         self._qkv = FusedProjection(mods) if can_fuse(mods) else None
 
     def forward(self, x, cos, sin, B, S, residual=None, cache: KVCache | None = None, start: int = 0,
-                kv_lens=None):
+                kv_lens=None, packed=None):
         tr = self.training
         qkv = project([self.q_proj, self.k_proj, self.v_proj], x, None, tr, self._qkv)
         if self.q_norm is not None:
@@ -179,7 +202,9 @@ class Qwen3Attention(nn.Module):
             q = apply_rope(qkv[:, :nq].reshape(T, self.hq, self.d), cos, sin).reshape(T, nq)
             k = apply_rope(qkv[:, nq:nq + nk].reshape(T, self.hkv, self.d), cos, sin).reshape(T, nk)
             v = qkv[:, nq + nk:]
-        if cache is None:
+        if packed is not None:   # (cu_seqlens on the device, max_seqlen, host copy): attention stays inside each sequence
+            o = flash_attention_varlen(q, k, v, packed[0], packed[1], self.hq, self.hkv, self.d, cu_host=packed[2])
+        elif cache is None:
             o = flash_attention(q, k, v, B, S, self.hq, self.hkv, self.d, causal=True, kv_lens=kv_lens)
         elif isinstance(cache, PackedPrefill):
             o = cache.attend(self.layer_idx, q, k, v, self.hq, self.hkv, self.d, flash_attention)
@@ -256,9 +281,10 @@ class Qwen3DecoderLayer(nn.Module):
         self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
-    def forward(self, x, cos, sin, B, S, cache=None, start=0, kv_lens=None):
+    def forward(self, x, cos, sin, B, S, cache=None, start=0, kv_lens=None, packed=None):
         xn, skip = rms_norm_residual(x, self.input_layernorm.weight, self.input_layernorm.eps)
-        h = self.self_attn(xn, cos, sin, B, S, residual=skip, cache=cache, start=start, kv_lens=kv_lens)
+        h = self.self_attn(xn, cos, sin, B, S, residual=skip, cache=cache, start=start, kv_lens=kv_lens,
+                           packed=packed)
         hn, skip = rms_norm_residual(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.eps)
         return self.mlp(hn, residual=skip)
 
@@ -282,10 +308,38 @@ class Qwen3Model(nn.Module):
         ang = position_ids.reshape(-1).float()[:, None] * self.inv_freq[None, :]
         return (torch.cos(ang) * self.attn_factor).contiguous(), (torch.sin(ang) * self.attn_factor).contiguous()
 
-    def forward(self, input_ids, position_ids=None, cache: KVCache | None = None, kv_lens=None):
+    def _packed(self, cu_seqlens, max_seqlen, B, S, device):
+        """Validate the boundaries of a packed ``[B, S]`` batch (they index the flattened B·S tokens; every row
+        boundary must be one of them) → (cu_seqlens int32 on ``device``, max_seqlen, host list)."""
+        if isinstance(cu_seqlens, torch.Tensor):
+            cu_seqlens = cu_seqlens.reshape(-1)
+        cu = check_cu_seqlens(cu_seqlens, B * S)
+        longest = max(b - a for a, b in zip(cu, cu[1:]))
+        if max_seqlen is None:
+            max_seqlen = longest
+        elif int(max_seqlen) < longest:
+            raise ValueError(f"max_seqlen {max_seqlen} is smaller than the longest sequence ({longest})")
+        if longest > S or not set(range(0, B * S + 1, S)) <= set(cu):
+            raise ValueError("cu_seqlens: every row boundary of the [B, S] batch must be a sequence boundary")
+        dev = cu_seqlens.to(device=device, dtype=torch.int32) if isinstance(cu_seqlens, torch.Tensor) else \
+            torch.tensor(cu, dtype=torch.int32, device=device)
+        return dev, max(int(max_seqlen), 1), cu
+
+    def forward(self, input_ids, position_ids=None, cache: KVCache | None = None, kv_lens=None,
+                cu_seqlens=None, max_seqlen=None):
         B, S = input_ids.shape
         start = cache.len if cache is not None else 0
         decoding = cache is not None and cache.pos is not None and S == 1
+        packed = None
+        if cu_seqlens is not None:
+            if cache is not None or kv_lens is not None:
+                raise ValueError("cu_seqlens cannot be combined with a KV cache or an attention_mask")
+            packed = self._packed(cu_seqlens, max_seqlen, B, S, input_ids.device)
+            if position_ids is None:   # positions restart at 0 at every sequence start
+                cu = torch.tensor(packed[2], dtype=torch.long)
+                lens = cu[1:] - cu[:-1]
+                position_ids = (torch.arange(B * S) - torch.repeat_interleave(cu[:-1], lens)).view(B, S)
+                position_ids = position_ids.to(input_ids.device)
         if position_ids is None and not decoding and start == 0:
             # positions 0 .. S-1 (every training step, every fresh prefill): the cos / sin tables depend only on
             # (B, S) — computed once instead of ~7 small launches + their host time at the head of every step
@@ -309,9 +363,9 @@ class Qwen3Model(nn.Module):
             x = self.pp.enter(x)        # stages > 0: the previous stage's hidden states
         for layer in self.layers:
             if self.gradient_checkpointing and self.training and cache is None:
-                x = lora_checkpoint(layer, x, cos, sin, B, S, None, 0, kv_lens, **self.ckpt_kwargs)
+                x = lora_checkpoint(layer, x, cos, sin, B, S, None, 0, kv_lens, packed, **self.ckpt_kwargs)
             else:
-                x = layer(x, cos, sin, B, S, cache, start, kv_lens)
+                x = layer(x, cos, sin, B, S, cache, start, kv_lens, packed)
         if self.pp is not None:
             x = self.pp.exit(x)         # hand to the next stage; every stage gets the last one's output
         if decoding:
@@ -379,11 +433,21 @@ class Qwen3ForCausalLM(nn.Module):
     # -------------------------------------------------------------- forward
     def forward(self, input_ids, attention_mask=None, labels=None, position_ids=None,
                 past_key_values: KVCache | None = None, use_cache: bool = False,
-                return_logits: bool | None = None, num_micro_batches: int = 1, **_) -> CausalLMOutput:
+                return_logits: bool | None = None, num_micro_batches: int = 1, cu_seqlens=None, max_seqlen=None,
+                cu_seq_lens_q=None, cu_seq_lens_k=None, max_length_q=None, max_length_k=None, **_) -> CausalLMOutput:
         """``num_micro_batches=G`` treats the batch as G gradient-accumulation micro-batches
         run in ONE pass: the loss is the mean of the G per-micro-batch mean losses, exactly
-        what sequential accumulation of ``loss_i / G`` produces (same gradient)."""
+        what sequential accumulation of ``loss_i / G`` produces (same gradient).
+
+        ``cu_seqlens`` (int32 ``[N+1]`` over the flattened ``B*S`` tokens, every row boundary among its entries)
+        and ``max_seqlen`` mark a packed batch: attention stays inside each sequence and positions restart at each
+        sequence start.  HF's padding-free names (``cu_seq_lens_q/k``, ``max_length_q/k``, what
+        ``DataCollatorWithFlattening(return_flash_attn_kwargs=True)`` emits) are accepted as aliases."""
         B, S = input_ids.shape
+        cu_seqlens, max_seqlen = _packing_kwargs(cu_seqlens, max_seqlen, cu_seq_lens_q, cu_seq_lens_k, max_length_q,
+                                                 max_length_k)
+        if cu_seqlens is not None and (attention_mask is not None or past_key_values is not None):
+            raise ValueError("cu_seqlens cannot be combined with attention_mask or a KV cache")
         kv_lens = None
         if attention_mask is not None and (past_key_values is None or
                                            (past_key_values.len == 0 and past_key_values.pos is None)):
@@ -391,7 +455,7 @@ class Qwen3ForCausalLM(nn.Module):
             lens = am.sum(1).to(torch.int32)
             if torch.equal(am, (torch.arange(S, device=am.device)[None] < lens[:, None]).int()):
                 kv_lens = lens                     # right padding: exact via per-row key length
-        h = self.model(input_ids, position_ids, past_key_values, kv_lens)
+        h = self.model(input_ids, position_ids, past_key_values, kv_lens, cu_seqlens, max_seqlen)
         loss = logits = None
         if labels is not None:
             tgt = shift_labels(labels).reshape(-1)

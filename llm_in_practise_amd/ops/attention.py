@@ -13,6 +13,10 @@ backward — ``nn.MultiheadAttention(dropout=p)`` of the teaching models,
 suffix prefill: ``Sq`` new queries per row at absolute positions ``q_offs[b] + i`` over a KV cache
 of ``Skv`` rows (``Fine-Tuning/README.md`` vLLM APC / chunked prefill parity).
 
+:func:`flash_attention_varlen` is the packed form (FlashAttention-varlen contract): ``N`` sequences back to
+back in ``[T, H*D]``, boundaries in ``cu_seqlens [N+1]``; causal, attention never crosses a boundary (neat
+sample packing for SFT, the serving engine's packed prefill).
+
 The kernel returns the per-row log-sum-exp so the backward recomputes P instead of storing the
 S×S matrix.
 """
@@ -83,6 +87,64 @@ def flash_attention(q, k, v, batch: int, seqlen: int, hq: int, hkv: int, d: int,
         mask = torch.arange(seqlen, device=q.device)[None, :] < kv_lens[:, None]
     o = ref.attention(qb, kb, vb, causal=causal, key_padding_mask=mask, scale=scale, dropout_p=dropout_p)
     return o.reshape(batch * seqlen, hq * d)
+
+
+class _FlashAttnVarlenFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, hq, hkv, d, scale):
+        o, lse = native().attn_varlen_fwd(q, k, v, cu_seqlens, max_seqlen, hq, hkv, d, scale)
+        ctx.save_for_backward(q, k, v, o, lse, cu_seqlens)
+        ctx.meta = (max_seqlen, hq, hkv, d, scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, cu_seqlens = ctx.saved_tensors
+        max_seqlen, hq, hkv, d, scale = ctx.meta
+        dq, dk, dv = native().attn_varlen_bwd(do.contiguous(), q, k, v, o, lse, cu_seqlens, max_seqlen, hq, hkv, d,
+                                              scale)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def check_cu_seqlens(cu, total: int, max_seqlen: int | None = None) -> list[int]:
+    """Host-side validation of a ``cu_seqlens`` list / CPU tensor for ``total`` packed tokens: starts at 0, ends at
+    ``total``, non-decreasing, no sequence longer than ``max_seqlen``.  Returns it as a list."""
+    c = [int(x) for x in (cu.tolist() if isinstance(cu, torch.Tensor) else cu)]
+    if len(c) < 2 or c[0] != 0 or c[-1] != total:
+        raise ValueError(f"cu_seqlens must start at 0 and end at the token count {total}, got {c[:1]} .. {c[-1:]}")
+    lens = [b - a for a, b in zip(c, c[1:])]
+    if min(lens) < 0:
+        raise ValueError("cu_seqlens must be non-decreasing")
+    if max_seqlen is not None and max(lens) > max_seqlen:
+        raise ValueError(f"max_seqlen {max_seqlen} is smaller than the longest sequence ({max(lens)})")
+    return c
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens: torch.Tensor, max_seqlen: int, hq: int, hkv: int, d: int,
+                           scale: float | None = None, cu_host=None, dropout_p: float = 0.0) -> torch.Tensor:
+    """Causal attention over ``N`` packed sequences: ``q [T, Hq*D]``, ``k/v [T, Hkv*D]`` (strided views allowed),
+    sequence ``b`` = rows ``cu_seqlens[b] .. cu_seqlens[b+1] - 1`` (int32), ``max_seqlen`` ≥ the longest one.
+    ``cu_host`` is an already validated host copy of ``cu_seqlens`` (list); without it the boundaries are read
+    back and checked here (one device sync).  Zero-length sequences are legal."""
+    if dropout_p:
+        raise ValueError("flash_attention_varlen: attention dropout is not supported with cu_seqlens")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1:
+        raise TypeError("cu_seqlens must be a 1-D int32 tensor")
+    T = q.shape[0]
+    if cu_host is None:
+        cu_host = check_cu_seqlens(cu_seqlens.cpu(), T, max_seqlen)
+    scale = scale if scale is not None else 1.0 / math.sqrt(d)
+    if native_ok(q, d):
+        if not (_aligned(q, d) and _aligned(k, d) and _aligned(v, d)):
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        return fn_apply(_FlashAttnVarlenFn, q, k, v, cu_seqlens.to(q.device), int(max_seqlen), hq, hkv, d, scale)
+    outs = []
+    for a, b in zip(cu_host, cu_host[1:]):
+        if b > a:
+            o = ref.attention(q[a:b].reshape(1, b - a, hq, d), k[a:b].reshape(1, b - a, hkv, d),
+                              v[a:b].reshape(1, b - a, hkv, d), causal=True, scale=scale)
+            outs.append(o.reshape(b - a, hq * d))
+    return torch.cat(outs, 0) if outs else q.new_zeros(0, hq * d)
 
 
 @torch.no_grad()

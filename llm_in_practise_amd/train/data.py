@@ -110,6 +110,85 @@ class SFTDataset(Dataset):
         return self.examples[i]
 
 
+def pack_examples(examples: list[dict], cutoff_len: int, pad_id: int = 0) -> list[dict]:
+    """Neat packing (LLaMA-Factory ``neat_packing``): first-fit-decreasing of unpadded tokenised samples
+    (``{"input_ids", "labels"}`` lists; longer ones truncated to ``cutoff_len``) into rows of ``cutoff_len``.
+    A row = several whole samples + one trailing pad segment that is a sequence of its own (labels -100).
+    The first token of every sequence gets label -100: with shifted labels the previous sample's last token
+    would otherwise be trained to predict it.  Each row: ``input_ids``, ``labels``, ``position_ids`` (restart at
+    every sequence start), ``seq_lens`` (the row's sequence lengths, pad segment included) and ``samples`` (the
+    indices of the packed examples, in row order)."""
+    order = sorted(range(len(examples)), key=lambda i: -min(len(examples[i]["input_ids"]), cutoff_len))
+    bins: list[list[int]] = []
+    free: list[int] = []
+    for i in order:
+        n = min(len(examples[i]["input_ids"]), cutoff_len)
+        if n == 0:
+            continue
+        for b, f in enumerate(free):
+            if n <= f:
+                bins[b].append(i)
+                free[b] -= n
+                break
+        else:
+            bins.append([i])
+            free.append(cutoff_len - n)
+    rows = []
+    for members, f in zip(bins, free):
+        ids, labels, pos, lens = [], [], [], []
+        for i in members:
+            x = list(examples[i]["input_ids"][:cutoff_len])
+            y = list(examples[i]["labels"][:cutoff_len])
+            y[0] = -100
+            ids += x
+            labels += y
+            pos += range(len(x))
+            lens.append(len(x))
+        if f:
+            ids += [pad_id] * f
+            labels += [-100] * f
+            pos += range(f)
+            lens.append(f)
+        rows.append({"input_ids": ids, "labels": labels, "position_ids": pos, "seq_lens": lens, "samples": members})
+    return rows
+
+
+class PackedSFTDataset(Dataset):
+    """:class:`SFTDataset` samples, unpadded, neat-packed into rows of ``max_length`` (:func:`pack_examples`).
+    Use with :class:`PackedDataCollator`."""
+
+    def __init__(self, records: Iterable[dict], tokenizer, max_length: int = 512, **sft_kwargs):
+        sft_kwargs.pop("padding", None)
+        base = SFTDataset(records, tokenizer, max_length, padding="longest", **sft_kwargs)
+        ex = []
+        for e in base.examples:
+            n = sum(e["attention_mask"])
+            ex.append({"input_ids": e["input_ids"][:n], "labels": e["labels"][:n]})
+        self.tok = tokenizer
+        self.num_samples = len(ex)
+        self.num_tokens = sum(len(e["input_ids"]) for e in ex)
+        self.examples = pack_examples(ex, max_length, _pad_id(tokenizer))
+
+    def __len__(self):
+        return len(self.examples)
+
+    def __getitem__(self, i):
+        return self.examples[i]
+
+
+class PackedDataCollator:
+    """Stack packed rows into ``input_ids`` / ``labels`` / ``position_ids`` ``[B, S]`` plus ``cu_seqlens`` (int32,
+    over the flattened ``B*S`` tokens, every row boundary among its entries) and ``max_seqlen`` — the model's
+    packed-batch arguments."""
+
+    def __call__(self, rows: list[dict]) -> dict:
+        out = {k: torch.tensor([r[k] for r in rows], dtype=torch.long) for k in ("input_ids", "labels", "position_ids")}
+        lens = [n for r in rows for n in r["seq_lens"]]
+        out["cu_seqlens"] = torch.tensor([0] + lens, dtype=torch.int64).cumsum(0).to(torch.int32)
+        out["max_seqlen"] = max(lens)
+        return out
+
+
 def _assistant_only_labels(ids, n, tok, im_start, im_end):
     labels = [-100] * len(ids)
     asst = tok.encode("assistant", add_special_tokens=False)

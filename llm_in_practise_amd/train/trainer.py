@@ -450,7 +450,15 @@ class Trainer:
     def _micro_step(self, batches, fused):
         with self.timer.phase("fwd_bwd"):
             if fused:
-                cat = {k: torch.cat([b[k] for b in batches]) for k in batches[0]}
+                cat = {k: torch.cat([b[k] for b in batches]) for k in batches[0]
+                       if k not in ("cu_seqlens", "max_seqlen")}
+                if "cu_seqlens" in batches[0]:   # packed rows: boundaries index the flattened tokens of the whole batch
+                    offs, parts = 0, []
+                    for i, b in enumerate(batches):
+                        parts.append(b["cu_seqlens"][1 if i else 0:] + offs)
+                        offs += b["input_ids"].numel()
+                    cat["cu_seqlens"] = torch.cat(parts)
+                    cat["max_seqlen"] = max(int(b["max_seqlen"]) for b in batches)
                 loss = self.compute_loss(self.model, cat, num_micro_batches=len(batches))
                 # drop the previous step's spent autograd graph while this forward is queued on the
                 # GPU (freed at return, its teardown stalled the launch queue before the optimizer)

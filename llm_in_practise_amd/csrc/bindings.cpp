@@ -169,12 +169,38 @@ const T* optr_t(const optional<Tensor>& t) {
 }
 
 // ------------------------------------------------------------------ norms
+// Every argument check below runs on the host before anything is launched: the kernels index with the
+// shapes they are told and convert with the dtype they are told, so a mismatch is an error here.
+constexpr int kNormMaxN = 8192;  // widest row of the one-wave-per-row kernels (CH = 16 chunks of 512)
+
+// x [.., N] (fp32 or bf16, contiguous, on the GPU), N % 8 == 0, N <= kNormMaxN; w / b [N] of x's dtype
+void check_norm_x(const char* op, const Tensor& x, const optional<Tensor>& w, const optional<Tensor>& b) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() >= 1, op, ": x must be a contiguous GPU tensor");
+  dtype_code(x);
+  const int64_t N = x.size(-1);
+  TORCH_CHECK(N > 0 && N % 8 == 0, op, ": hidden size must be a multiple of 8, got ", N);
+  TORCH_CHECK(N <= kNormMaxN, op, ": hidden size ", N, " exceeds the kernel's row limit of ", kNormMaxN);
+  TORCH_CHECK(x.numel() / N <= INT_MAX, op, ": too many rows");
+  for (const optional<Tensor>* t : {&w, &b}) {
+    if (t->has_value() && (*t)->defined())
+      TORCH_CHECK((*t)->is_cuda() && (*t)->scalar_type() == x.scalar_type() && (*t)->is_contiguous() &&
+                      (*t)->numel() == N,
+                  op, ": weight / bias must be contiguous [N] of x's dtype");
+  }
+}
+// dy like x; the saved row statistics fp32 [M]
+void check_norm_bwd(const char* op, const Tensor& dy, const Tensor& x, std::initializer_list<const Tensor*> stats) {
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.scalar_type() == x.scalar_type() && dy.sizes() == x.sizes(),
+              op, ": dy must be contiguous with x's shape and dtype");
+  const int64_t M = x.numel() / x.size(-1);
+  for (const Tensor* t : stats)
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == M, op,
+                ": rstd / mean must be contiguous fp32 [rows]");
+}
+
 std::vector<Tensor> rmsnorm_fwd(Tensor x, optional<Tensor> w, double eps) {
-  CHECK_CUDA(x);
-  CHECK_CONTIG(x);
+  check_norm_x("rmsnorm_fwd", x, w, c10::nullopt);
   const int N = x.size(-1), M = x.numel() / N;
-  TORCH_CHECK(N % 8 == 0, "rmsnorm: hidden size must be a multiple of 8");
-  if (w) TORCH_CHECK(w->scalar_type() == x.scalar_type() && w->is_contiguous(), "rmsnorm weight dtype/layout");
   auto y = at::empty_like(x);
   auto rstd = at::empty({M}, x.options().dtype(at::kFloat));
   launch_rmsnorm_fwd(dtype_code(x), x.data_ptr(), optr(w), y.data_ptr(), rstd.data_ptr<float>(), M, N, (float)eps,
@@ -184,10 +210,11 @@ std::vector<Tensor> rmsnorm_fwd(Tensor x, optional<Tensor> w, double eps) {
 
 std::vector<Tensor> rmsnorm_bwd(Tensor dy, Tensor x, optional<Tensor> w, Tensor rstd, bool need_dw,
                                 optional<Tensor> dres) {
-  CHECK_CONTIG(dy);
-  CHECK_CONTIG(x);
+  check_norm_x("rmsnorm_bwd", x, w, c10::nullopt);
+  check_norm_bwd("rmsnorm_bwd", dy, x, {&rstd});
   if (dres && dres->defined()) {
-    TORCH_CHECK(dres->is_contiguous() && dres->sizes() == x.sizes() && dres->scalar_type() == x.scalar_type(),
+    TORCH_CHECK(dres->is_cuda() && dres->is_contiguous() && dres->sizes() == x.sizes() &&
+                    dres->scalar_type() == x.scalar_type(),
                 "rmsnorm_bwd: dres must match x");
   }
   const int N = x.size(-1), M = x.numel() / N;
@@ -204,10 +231,8 @@ std::vector<Tensor> rmsnorm_bwd(Tensor dy, Tensor x, optional<Tensor> w, Tensor 
 }
 
 std::vector<Tensor> layernorm_fwd(Tensor x, optional<Tensor> w, optional<Tensor> b, double eps) {
-  CHECK_CUDA(x);
-  CHECK_CONTIG(x);
+  check_norm_x("layernorm_fwd", x, w, b);
   const int N = x.size(-1), M = x.numel() / N;
-  TORCH_CHECK(N % 8 == 0, "layernorm: hidden size must be a multiple of 8");
   auto y = at::empty_like(x);
   auto mean = at::empty({M}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({M}, x.options().dtype(at::kFloat));
@@ -217,6 +242,8 @@ std::vector<Tensor> layernorm_fwd(Tensor x, optional<Tensor> w, optional<Tensor>
 }
 
 std::vector<Tensor> layernorm_bwd(Tensor dy, Tensor x, optional<Tensor> w, Tensor mean, Tensor rstd, bool need_dw) {
+  check_norm_x("layernorm_bwd", x, w, c10::nullopt);
+  check_norm_bwd("layernorm_bwd", dy, x, {&mean, &rstd});
   const int N = x.size(-1), M = x.numel() / N;
   auto dx = at::empty_like(x);
   Tensor part, dw, db;
@@ -233,22 +260,51 @@ std::vector<Tensor> layernorm_bwd(Tensor dy, Tensor x, optional<Tensor> w, Tenso
 }
 
 // ------------------------------------------------------------------ rope
+// cos / sin: fp32 [T, D/2], contiguous, on the GPU
+void check_rope_tables(const char* op, const Tensor& cos, const Tensor& sin, int64_t T, int64_t half) {
+  for (const Tensor* t : {&cos, &sin})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2 &&
+                    t->size(0) == T && t->size(1) == half,
+                op, ": cos / sin must be contiguous fp32 [T, D/2]");
+}
+
 Tensor rope(Tensor x, Tensor cos, Tensor sin, bool interleaved, bool inverse) {
-  CHECK_CONTIG(x);
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "rope: x must be a contiguous GPU tensor");
   TORCH_CHECK(x.dim() == 3, "rope expects [T, H, D]");
+  TORCH_CHECK(x.size(2) % 2 == 0, "rope: head_dim must be even, got ", x.size(2));
+  TORCH_CHECK(x.size(0) <= INT_MAX && x.size(1) <= INT_MAX && x.size(2) <= INT_MAX, "rope: dimension too large");
+  check_rope_tables("rope", cos, sin, x.size(0), x.size(2) / 2);
   auto y = at::empty_like(x);
   launch_rope(dtype_code(x), x.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(), y.data_ptr(), x.size(0),
               x.size(1), x.size(2), interleaved, inverse, stream());
   return y;
 }
 
-std::vector<Tensor> qk_norm_rope_fwd(Tensor qkv, optional<Tensor> qw, optional<Tensor> kw, Tensor cos, Tensor sin,
-                                     int64_t hq, int64_t hkv, int64_t d, double eps) {
+// head dims the fused q/k norm + rope kernels are instantiated for (rope.hip)
+bool qk_norm_rope_dim_ok(int64_t d) { return d == 32 || d == 64 || d == 128 || d == 256; }
+
+void check_qk_norm_rope(const char* op, const Tensor& qkv, const optional<Tensor>& qw, const optional<Tensor>& kw,
+                        const Tensor& cos, const Tensor& sin, int64_t hq, int64_t hkv, int64_t d) {
+  TORCH_CHECK(qk_norm_rope_dim_ok(d), op, ": head_dim must be 32, 64, 128 or 256, got ", d);
+  TORCH_CHECK(hq > 0 && hkv > 0, op, ": head counts must be positive");
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2, op, ": qkv must be a GPU tensor [T, (hq+2hkv)*d]");
   CHECK_BF16(qkv);
   CHECK_CONTIG(qkv);
+  TORCH_CHECK(qkv.size(1) == (hq + 2 * hkv) * d, op, ": qkv width mismatch");
+  TORCH_CHECK(qkv.numel() <= INT_MAX, op, ": qkv too large");
+  check_rope_tables(op, cos, sin, qkv.size(0), d / 2);
+  for (const optional<Tensor>* t : {&qw, &kw}) {
+    if (t->has_value() && (*t)->defined())
+      TORCH_CHECK((*t)->is_cuda() && (*t)->scalar_type() == at::kBFloat16 && (*t)->is_contiguous() &&
+                      (*t)->numel() == d,
+                  op, ": q / k norm weight must be contiguous bf16 [d]");
+  }
+}
+
+std::vector<Tensor> qk_norm_rope_fwd(Tensor qkv, optional<Tensor> qw, optional<Tensor> kw, Tensor cos, Tensor sin,
+                                     int64_t hq, int64_t hkv, int64_t d, double eps) {
+  check_qk_norm_rope("qk_norm_rope_fwd", qkv, qw, kw, cos, sin, hq, hkv, d);
   const int T = qkv.size(0);
-  TORCH_CHECK(qkv.size(1) == (hq + 2 * hkv) * d, "qkv width mismatch");
-  TORCH_CHECK(cos.scalar_type() == at::kFloat && cos.size(0) == T && cos.size(1) == d / 2, "cos table [T, D/2] fp32");
   auto q = at::empty({T, hq * d}, qkv.options());
   auto k = at::empty({T, hkv * d}, qkv.options());
   auto rq = at::empty({T * hq}, qkv.options().dtype(at::kFloat));
@@ -262,7 +318,18 @@ std::vector<Tensor> qk_norm_rope_fwd(Tensor qkv, optional<Tensor> qw, optional<T
 Tensor qk_norm_rope_bwd(Tensor dq, Tensor dk, optional<Tensor> dv, Tensor qkv, optional<Tensor> qw,
                         optional<Tensor> kw, Tensor cos, Tensor sin, Tensor rq, Tensor rk, int64_t hq, int64_t hkv,
                         int64_t d) {
+  check_qk_norm_rope("qk_norm_rope_bwd", qkv, qw, kw, cos, sin, hq, hkv, d);
   const int T = qkv.size(0);
+  TORCH_CHECK(dq.is_cuda() && dq.scalar_type() == at::kBFloat16 && dq.is_contiguous() &&
+                  dq.numel() == (int64_t)T * hq * d,
+              "qk_norm_rope_bwd: dq must be contiguous bf16 [T, hq*d]");
+  TORCH_CHECK(dk.is_cuda() && dk.scalar_type() == at::kBFloat16 && dk.is_contiguous() &&
+                  dk.numel() == (int64_t)T * hkv * d,
+              "qk_norm_rope_bwd: dk must be contiguous bf16 [T, hkv*d]");
+  TORCH_CHECK(rq.is_cuda() && rq.scalar_type() == at::kFloat && rq.is_contiguous() && rq.numel() == (int64_t)T * hq &&
+                  rk.is_cuda() && rk.scalar_type() == at::kFloat && rk.is_contiguous() &&
+                  rk.numel() == (int64_t)T * hkv,
+              "qk_norm_rope_bwd: rq / rk must be contiguous fp32 [T*hq] / [T*hkv]");
   auto dqkv = at::empty_like(qkv);
   const void* dvp = nullptr;
   if (dv && dv->defined()) {
@@ -280,10 +347,11 @@ Tensor qk_norm_rope_bwd(Tensor dq, Tensor dk, optional<Tensor> dv, Tensor qkv, o
 
 // ------------------------------------------------------------------ activations
 Tensor swiglu_fwd(Tensor gu) {
+  CHECK_CUDA(gu);
   CHECK_BF16(gu);
   CHECK_CONTIG(gu);
+  TORCH_CHECK(gu.dim() >= 1 && gu.size(-1) % 16 == 0, "swiglu: intermediate size must be a multiple of 8");
   const int F = gu.size(-1) / 2, M = gu.numel() / gu.size(-1);
-  TORCH_CHECK(F % 8 == 0, "swiglu: intermediate size must be a multiple of 8");
   auto sizes = gu.sizes().vec();
   sizes.back() = F;
   auto y = at::empty(sizes, gu.options());
@@ -291,18 +359,31 @@ Tensor swiglu_fwd(Tensor gu) {
   return y;
 }
 Tensor swiglu_bwd(Tensor dy, Tensor gu) {
+  TORCH_CHECK(gu.is_cuda() && dy.is_cuda(), "swiglu_bwd: GPU tensors");
+  CHECK_BF16(gu);
+  CHECK_CONTIG(gu);
+  CHECK_BF16(dy);
+  CHECK_CONTIG(dy);
+  TORCH_CHECK(gu.dim() >= 1 && gu.size(-1) % 16 == 0, "swiglu: intermediate size must be a multiple of 8");
   const int F = gu.size(-1) / 2, M = gu.numel() / gu.size(-1);
+  TORCH_CHECK(dy.dim() == gu.dim() && dy.size(-1) == F && dy.numel() == (int64_t)M * F,
+              "swiglu_bwd: dy must be [.., F] for gu [.., 2F]");
   auto dgu = at::empty_like(gu);
   launch_swiglu_bwd(dy.data_ptr(), gu.data_ptr(), dgu.data_ptr(), M, F, stream());
   return dgu;
 }
 Tensor gelu_fwd(Tensor x) {
+  CHECK_CUDA(x);
   CHECK_CONTIG(x);
   auto y = at::empty_like(x);
   launch_gelu_fwd(dtype_code(x), x.data_ptr(), y.data_ptr(), x.numel(), stream());
   return y;
 }
 Tensor gelu_bwd(Tensor dy, Tensor x) {
+  TORCH_CHECK(x.is_cuda() && dy.is_cuda(), "gelu_bwd: GPU tensors");
+  CHECK_CONTIG(x);
+  TORCH_CHECK(dy.is_contiguous() && dy.scalar_type() == x.scalar_type() && dy.sizes() == x.sizes(),
+              "gelu_bwd: dy must be contiguous with x's shape and dtype");
   auto dx = at::empty_like(x);
   launch_gelu_bwd(dtype_code(x), dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), stream());
   return dx;
@@ -341,23 +422,35 @@ Tensor embedding_bwd(Tensor dout, Tensor ids, int64_t V, int64_t padding_idx) {
 }
 
 Tensor dropout_fwd(Tensor x, double p, int64_t key) {
+  CHECK_CUDA(x);
   CHECK_BF16(x);
   CHECK_CONTIG(x);
   TORCH_CHECK(x.numel() % 8 == 0, "dropout: numel % 8");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout: p in [0, 1)");
   auto y = at::empty_like(x);
   launch_dropout_fwd(x.data_ptr(), y.data_ptr(), x.numel(), (uint64_t)key, (float)p, stream());
   return y;
 }
 void dropout_bwd_add(Tensor dx, Tensor t, double p, int64_t key) {
+  TORCH_CHECK(dx.is_cuda() && t.is_cuda(), "dropout_bwd_add: GPU tensors");
+  CHECK_BF16(dx);
+  CHECK_BF16(t);
   CHECK_CONTIG(dx);
   CHECK_CONTIG(t);
+  TORCH_CHECK(dx.numel() % 8 == 0, "dropout: numel % 8");
+  TORCH_CHECK(t.numel() == dx.numel(), "dropout_bwd_add: dx and t must have the same number of elements");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout: p in [0, 1)");
   launch_dropout_bwd_add(dx.data_ptr(), t.data_ptr(), dx.numel(), (uint64_t)key, (float)p, stream());
 }
 
 // ------------------------------------------------------------------ cross entropy
 Tensor ce_fwd_bwd(Tensor logits, Tensor labels, int64_t ignore_index, Tensor scale) {
+  CHECK_CUDA(logits);
   CHECK_CONTIG(logits);
-  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels int64");
+  TORCH_CHECK(logits.dim() == 2, "ce_fwd_bwd: logits [rows, vocab]");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda() && labels.numel() == logits.size(0),
+              "labels int64, one per row, on the GPU");
+  TORCH_CHECK(scale.is_cuda(), "ce_fwd_bwd: scale must be a GPU tensor");
   const int M = logits.size(0), V = logits.size(1);
   TORCH_CHECK(V % 8 == 0, "vocab must be a multiple of 8");
   auto loss = at::empty({M}, logits.options().dtype(at::kFloat));
@@ -371,8 +464,28 @@ Tensor ce_fwd_bwd(Tensor logits, Tensor labels, int64_t ignore_index, Tensor sca
 }
 
 // ------------------------------------------------------------------ optimizers
+// gscale: fp32 {norm, clip coefficient, ..} (grad_norm's output); skip: fp32 overflow flag; p16: bf16 mirror of p
+void check_optim_aux(const char* op, const Tensor& p, const optional<Tensor>& p16, const optional<Tensor>& gscale,
+                     const optional<Tensor>& skip) {
+  if (p16 && p16->defined())
+    TORCH_CHECK(p16->is_cuda() && p16->scalar_type() == at::kBFloat16 && p16->is_contiguous() &&
+                    p16->numel() == p.numel(),
+                op, ": p16 must be a contiguous bf16 mirror of p");
+  if (gscale && gscale->defined())
+    TORCH_CHECK(gscale->is_cuda() && gscale->scalar_type() == at::kFloat && gscale->is_contiguous() &&
+                    gscale->numel() >= 2,
+                op, ": gscale must be contiguous fp32 {norm, coefficient}");
+  if (skip && skip->defined())
+    TORCH_CHECK(skip->is_cuda() && skip->scalar_type() == at::kFloat && skip->numel() >= 1, op,
+                ": skip must be an fp32 flag on the GPU");
+}
+
 Tensor grad_norm(Tensor g, double max_norm, optional<Tensor> out, bool accumulate) {
+  CHECK_CUDA(g);
   CHECK_CONTIG(g);
+  if (out && out->defined())
+    TORCH_CHECK(out->is_cuda() && out->scalar_type() == at::kFloat && out->is_contiguous() && out->numel() >= 3,
+                "grad_norm: out must be contiguous fp32 [3] on the GPU");
   Tensor o = out && out->defined() ? *out : at::zeros({3}, g.options().dtype(at::kFloat));
   auto part = at::empty({1024}, g.options().dtype(at::kFloat));
   launch_grad_norm(dtype_code(g), g.data_ptr(), g.numel(), part.data_ptr<float>(), o.data_ptr<float>(),
@@ -385,6 +498,10 @@ void adamw(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> p16, double 
   TORCH_CHECK(p.scalar_type() == at::kFloat && m.scalar_type() == at::kFloat && v.scalar_type() == at::kFloat,
               "adamw: fp32 master/state");
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(), "adamw: contiguous");
+  TORCH_CHECK(p.is_cuda() && g.is_cuda() && m.is_cuda() && v.is_cuda(), "adamw: GPU tensors");
+  TORCH_CHECK(g.numel() == p.numel() && m.numel() == p.numel() && v.numel() == p.numel(),
+              "adamw: p, g, m and v must have the same number of elements");
+  check_optim_aux("adamw", p, p16, gscale, skip);
   const float bc1 = 1.f - std::pow((float)b1, (float)step), bc2 = 1.f - std::pow((float)b2, (float)step);
   launch_adamw(dtype_code(g), p.data_ptr<float>(), g.data_ptr(), m.data_ptr<float>(), v.data_ptr<float>(),
                (void*)optr(p16), p.numel(), lr, b1, b2, eps, wd, bc1, bc2, optr_t<float>(gscale), optr_t<float>(skip),
@@ -413,6 +530,23 @@ Tensor host_mapped_empty(int64_t numel, at::ScalarType dtype) {
 void adamw8bit(Tensor p, Tensor g, Tensor qm, Tensor qv, Tensor am, Tensor av, Tensor code_s, Tensor code_u,
                optional<Tensor> p16, double lr, double b1, double b2, double eps, double wd, int64_t step,
                optional<Tensor> gscale, optional<Tensor> skip) {
+  TORCH_CHECK(p.is_cuda() && g.is_cuda() && qm.is_cuda() && qv.is_cuda() && am.is_cuda() && av.is_cuda() &&
+                  code_s.is_cuda() && code_u.is_cuda(),
+              "adamw8bit: GPU tensors");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && am.scalar_type() == at::kFloat && av.scalar_type() == at::kFloat &&
+                  code_s.scalar_type() == at::kFloat && code_u.scalar_type() == at::kFloat,
+              "adamw8bit: fp32 master, absmax and code maps");
+  TORCH_CHECK(qm.scalar_type() == at::kByte && qv.scalar_type() == at::kByte, "adamw8bit: uint8 state codes");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && qm.is_contiguous() && qv.is_contiguous() &&
+                  am.is_contiguous() && av.is_contiguous() && code_s.is_contiguous() && code_u.is_contiguous(),
+              "adamw8bit: contiguous");
+  const int64_t n8 = p.numel(), blocks8 = (n8 + 255) / 256;
+  TORCH_CHECK(g.numel() == n8 && qm.numel() == n8 && qv.numel() == n8,
+              "adamw8bit: p, g, qm and qv must have the same number of elements");
+  TORCH_CHECK(am.numel() >= blocks8 && av.numel() >= blocks8, "adamw8bit: am / av need one absmax per 256-element block (",
+              blocks8, ")");
+  TORCH_CHECK(code_s.numel() == 256 && code_u.numel() == 256, "adamw8bit: code maps have 256 entries");
+  check_optim_aux("adamw8bit", p, p16, gscale, skip);
   const float bc1 = 1.f - std::pow((float)b1, (float)step), bc2 = 1.f - std::pow((float)b2, (float)step);
   launch_adamw8bit(dtype_code(g), p.data_ptr<float>(), g.data_ptr(), qm.data_ptr<uint8_t>(), qv.data_ptr<uint8_t>(),
                    am.data_ptr<float>(), av.data_ptr<float>(), code_s.data_ptr<float>(), code_u.data_ptr<float>(),
@@ -421,6 +555,11 @@ void adamw8bit(Tensor p, Tensor g, Tensor qm, Tensor qv, Tensor am, Tensor av, T
 }
 
 void unscale(Tensor g, Tensor inv_scale, Tensor found_inf) {
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous(), "unscale: g must be a contiguous GPU tensor");
+  TORCH_CHECK(inv_scale.is_cuda() && inv_scale.scalar_type() == at::kFloat && inv_scale.numel() >= 1,
+              "unscale: inv_scale must be an fp32 GPU tensor");
+  TORCH_CHECK(found_inf.is_cuda() && found_inf.scalar_type() == at::kFloat && found_inf.numel() >= 1,
+              "unscale: found_inf must be an fp32 GPU tensor");
   launch_unscale(dtype_code(g), g.data_ptr(), g.numel(), inv_scale.data_ptr<float>(), found_inf.data_ptr<float>(),
                  stream());
 }

@@ -50,6 +50,8 @@ __global__ __launch_bounds__(NT) void ce_fwd_bwd_k(T* __restrict__ logits, const
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx = fmaxf(mx, x[i]);
     const float mn = fmaxf(m, mx);
+    // nothing but -inf so far (a masked vocabulary range): (m, s) stay (-inf, 0); m - mn would be inf - inf
+    if (mn == -INFINITY) continue;
     float acc = s * __expf(m - mn);
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc += __expf(x[i] - mn);

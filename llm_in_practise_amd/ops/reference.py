@@ -144,3 +144,187 @@ def adamw_step(p, g, m, v, step: int, lr: float, beta1: float, beta2: float, eps
     bc2 = 1 - beta2 ** step
     denom = (v / bc2).sqrt().add_(eps)
     p.addcdiv_(m, denom, value=-lr / bc1)
+
+
+# ----------------------------------------------------------------------------- fp64 per-element oracles
+# The functions below compute in fp64 from the inputs exactly as the kernels read them (bf16 / fp32 values
+# widened, never re-rounded) and return, next to each result, the magnitude of the largest intermediate
+# that feeds every element.  The per-element test bound is judged against that magnitude, so an output
+# that is the small difference of large terms is not held to an accuracy its operands cannot carry.
+def _d(t):
+    return None if t is None else t.detach().double()
+
+
+def rmsnorm_fwd64(x, w, eps: float):
+    """-> y, rstd (fp64)."""
+    x, w = _d(x), _d(w)
+    r = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    y = x * r
+    if w is not None:
+        y = y * w
+    return y, r.squeeze(-1)
+
+
+def rmsnorm_bwd64(dy, x, w, eps: float, dres=None):
+    """-> dx, S(dx), dw, S(dw): dx = r·(w·dy − x̂·mean(x̂·w·dy)) (+ dres), dw = Σ_rows dy·x̂."""
+    dy, x, w, dres = _d(dy), _d(x), _d(w), _d(dres)
+    r = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    xh = x * r
+    wg = dy if w is None else dy * w
+    dot = (xh * wg).mean(-1, keepdim=True)
+    dx = r * (wg - xh * dot)
+    s_dx = r * (wg.abs() + (xh * dot).abs())
+    if dres is not None:
+        dx = dx + dres
+        s_dx = s_dx + dres.abs()
+    terms = (dy * xh).reshape(-1, x.shape[-1])
+    return dx, s_dx, terms.sum(0), terms.abs().sum(0)
+
+
+def layernorm_fwd64(x, w, b, eps: float):
+    """-> y, S(y), mean, rstd."""
+    x, w, b = _d(x), _d(w), _d(b)
+    mu = x.mean(-1, keepdim=True)
+    r = torch.rsqrt((x - mu).pow(2).mean(-1, keepdim=True) + eps)
+    y = (x - mu) * r
+    s = (x.abs() + mu.abs()) * r
+    if w is not None:
+        y, s = y * w, s * w.abs()
+    if b is not None:
+        y, s = y + b, s + b.abs()
+    return y, s, mu.squeeze(-1), r.squeeze(-1)
+
+
+def layernorm_bwd64(dy, x, w, eps: float):
+    """-> dx, S(dx), dw, S(dw), db, S(db): dx = r·(wg − s1 − x̂·s2), s1 = mean(wg), s2 = mean(wg·x̂)."""
+    dy, x, w = _d(dy), _d(x), _d(w)
+    mu = x.mean(-1, keepdim=True)
+    r = torch.rsqrt((x - mu).pow(2).mean(-1, keepdim=True) + eps)
+    xh = (x - mu) * r
+    wg = dy if w is None else dy * w
+    s1 = wg.mean(-1, keepdim=True)
+    s2 = (wg * xh).mean(-1, keepdim=True)
+    dx = r * (wg - s1 - xh * s2)
+    s_dx = r * (wg.abs() + s1.abs() + (xh * s2).abs())
+    N = x.shape[-1]
+    tw, tb = (dy * xh).reshape(-1, N), dy.reshape(-1, N)
+    s_tw = (dy.abs() * (x.abs() + mu.abs()) * r).reshape(-1, N)   # x̂ is itself the difference x − mean
+    return dx, s_dx, tw.sum(0), s_tw.sum(0), tb.sum(0), tb.abs().sum(0)
+
+
+def rope64(x, cos, sin, interleaved: bool = False, inverse: bool = False):
+    """x [T, H, D], cos/sin [T, D/2] -> y, S(y) (the two products that meet in every output)."""
+    x, c, s = _d(x), _d(cos)[:, None, :], _d(sin)[:, None, :]
+    if inverse:
+        s = -s
+    if interleaved:
+        x1, x2 = x[..., 0::2], x[..., 1::2]
+    else:
+        h = x.shape[-1] // 2
+        x1, x2 = x[..., :h], x[..., h:]
+    o1, o2 = x1 * c - x2 * s, x2 * c + x1 * s
+    a1, a2 = (x1 * c).abs() + (x2 * s).abs(), (x2 * c).abs() + (x1 * s).abs()
+    if interleaved:
+        return torch.stack([o1, o2], -1).flatten(-2), torch.stack([a1, a2], -1).flatten(-2)
+    return torch.cat([o1, o2], -1), torch.cat([a1, a2], -1)
+
+
+def qk_norm_rope64(qkv, qw, kw, cos, sin, hq: int, hkv: int, d: int, eps: float, dq, dk):
+    """The fused per-head q/k RMSNorm + rotate-half RoPE on qkv [T, (hq+2hkv)·d] and its backward.
+    -> (q, S(q), k, S(k)), dqkv[:, :(hq+hkv)·d], S(dqkv).  Forward: the normed value is rounded to bf16 before
+    the rotation (as Qwen3 does).  Backward: the rotation inverted, then the norm backward on the unrounded x̂."""
+    T = qkv.shape[0]
+    outs, grads, scales = [], [], []
+    for lo, h, w, g in ((0, hq, qw, dq), (hq * d, hkv, kw, dk)):
+        x = _d(qkv[:, lo:lo + h * d]).reshape(T, h, d)
+        wd = torch.ones(d, device=qkv.device, dtype=torch.float64) if w is None else _d(w)
+        r = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+        xn = (x * r * wd).to(torch.bfloat16)
+        o, s_o = rope64(xn, cos, sin)
+        outs += [o.reshape(T, h * d), s_o.reshape(T, h * d)]
+        gi, s_gi = rope64(g.reshape(T, h, d), cos, sin, False, True)
+        xh, wg = x * r, gi * wd
+        dot = (xh * wg).mean(-1, keepdim=True)
+        grads.append((r * (wg - xh * dot)).reshape(T, h * d))
+        scales.append((r * (s_gi * wd.abs() + (xh * dot).abs())).reshape(T, h * d))
+    return outs, torch.cat(grads, 1), torch.cat(scales, 1)
+
+
+def swiglu_fwd64(gu):
+    gu = _d(gu)
+    F_ = gu.shape[-1] // 2
+    g, u = gu[..., :F_], gu[..., F_:]
+    return g * torch.sigmoid(g) * u
+
+
+def swiglu_bwd64(dy, gu):
+    """-> dgu = [dy·u·silu'(g) | dy·silu(g)], S(dgu) (silu' = σ + g·σ·(1−σ): two terms that can cancel)."""
+    dy, gu = _d(dy), _d(gu)
+    F_ = gu.shape[-1] // 2
+    g, u = gu[..., :F_], gu[..., F_:]
+    sg = torch.sigmoid(g)
+    t = g * sg * (1 - sg)
+    dg = dy * u * (sg + t)
+    du = dy * g * sg
+    return torch.cat([dg, du], -1), torch.cat([(dy * u).abs() * (sg + t.abs()), du.abs()], -1)
+
+
+def gelu_fwd64(x):
+    """-> y, S(y): y = ½x(1 + erf(x/√2)); for x < 0 the sum 1 + erf cancels against operands of size 1."""
+    x = _d(x)
+    e = torch.erf(x * 0.7071067811865476)
+    return 0.5 * x * (1 + e), 0.5 * x.abs() * (1 + e.abs())
+
+
+def gelu_bwd64(dy, x):
+    dy, x = _d(dy), _d(x)
+    e = torch.erf(x * 0.7071067811865476)
+    pdf = 0.3989422804014327 * torch.exp(-0.5 * x * x)
+    return dy * (0.5 * (1 + e) + x * pdf), dy.abs() * (0.5 * (1 + e.abs()) + (x * pdf).abs())
+
+
+def ce_fwd_bwd64(logits, labels, ignore_index: int, row_scale):
+    """-> row loss, dlogits = (softmax − onehot)·scale, S(dlogits) = (softmax + onehot)·|scale|.
+    ``row_scale`` [M]: the scale of every row.  Ignored rows: zeros, loss 0."""
+    x = _d(logits)
+    keep = labels != ignore_index
+    lab = torch.where(keep, labels, torch.zeros_like(labels))
+    lse = torch.logsumexp(x, -1)
+    p = torch.exp(x - lse[:, None])
+    one = torch.zeros_like(p).scatter_(1, lab[:, None], 1.0)
+    sc = (_d(row_scale) * keep)[:, None]
+    loss = torch.where(keep, lse - x.gather(1, lab[:, None]).squeeze(1), torch.zeros_like(lse))
+    return loss, (p - one) * sc, (p + one) * sc.abs()
+
+
+def adamw_step64(p, g, m, v, step: int, lr, b1, b2, eps, wd):
+    """One AdamW step in fp64 (out of place) -> p, S(p), m, S(m), v.  p is the difference of the decayed weight
+    and the update, m the sum of two terms of either sign: S is the sum of their magnitudes."""
+    p, g, m, v = _d(p), _d(g), _d(m), _d(v)
+    s_m = (b1 * m).abs() + ((1 - b1) * g).abs()
+    m = b1 * m + (1 - b1) * g
+    v = b2 * v + (1 - b2) * g * g
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    upd = (lr / bc1) * m / ((v / bc2).sqrt() + eps)
+    dec = p * (1 - lr * wd)
+    return dec - upd, dec.abs() + upd.abs(), m, s_m, v
+
+
+def adamw8bit_step64(p, g, qm, qv, am, av, code_s, code_u, step: int, lr, b1, b2, eps, wd, block: int = 256):
+    """One blockwise 8-bit AdamW step in fp64 from the stored (quantised) state: dequantise, update, per-block
+    absmax.  -> p, S(p), m, v (the updated moments before requantisation), am, av.  The requantised code of an
+    element is the map entry nearest m/am (v/av)."""
+    n = p.numel()
+    nb = (n + block - 1) // block
+    bi = torch.arange(n, device=p.device) // block
+    m = _d(code_s)[qm.long()] * _d(am)[bi]
+    v = _d(code_u)[qv.long()] * _d(av)[bi]
+    g = _d(g)
+    m = b1 * m + (1 - b1) * g
+    v = b2 * v + (1 - b2) * g * g
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    dec, upd = _d(p) * (1 - lr * wd), (lr / bc1) * m / ((v / bc2).sqrt() + eps)
+    p, s_p = dec - upd, dec.abs() + upd.abs()
+    am2 = torch.zeros(nb, dtype=torch.float64, device=p.device).scatter_reduce_(0, bi, m.abs(), "amax")
+    av2 = torch.zeros(nb, dtype=torch.float64, device=p.device).scatter_reduce_(0, bi, v, "amax")
+    return p, s_p, m, v, am2, av2

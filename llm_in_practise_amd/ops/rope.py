@@ -59,19 +59,25 @@ class _QKNormRopeFn(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None, None, None
 
 
+# head dims the fused kernel is instantiated for (csrc/kernels/rope.hip); the binding rejects any other
+QK_NORM_ROPE_DIMS = (32, 64, 128, 256)
+
+
 def qk_norm_rope(qkv: torch.Tensor, q_weight, k_weight, cos, sin, hq: int, hkv: int, d: int,
                  eps: float = 1e-6):
-    """Split fused ``qkv [T, (hq+2hkv)*d]``; RMS-normalise each q/k head (Qwen3 qk-norm) and
-    rotate (rotate-half).  Returns q ``[T, hq*d]``, k ``[T, hkv*d]``, v (strided view)."""
-    if use_native(qkv):
+    """Split fused ``qkv [T, (hq+2hkv)*d]``; RMS-normalise each q/k head (Qwen3 qk-norm, unit weight
+    without one) and rotate (rotate-half).  Returns q ``[T, hq*d]``, k ``[T, hkv*d]``, v (strided view).
+
+    A head_dim the fused kernel has no instantiation for (e.g. 96, which the attention kernels support)
+    runs the same composition — norm rounded to the model dtype, then RoPE — op by op, with autograd."""
+    if use_native(qkv) and d in QK_NORM_ROPE_DIMS:
         return fn_apply(_QKNormRopeFn, qkv.contiguous(), q_weight, k_weight, cos, sin, hq, hkv, d, eps)
     T = qkv.shape[0]
     q = qkv[:, : hq * d].reshape(T, hq, d)
     k = qkv[:, hq * d:(hq + hkv) * d].reshape(T, hkv, d)
     v = qkv[:, (hq + hkv) * d:]
-    if q_weight is not None:
-        q = ref.rmsnorm(q, q_weight, eps)
-        k = ref.rmsnorm(k, k_weight, eps)
+    q = ref.rmsnorm(q, q_weight, eps)
+    k = ref.rmsnorm(k, k_weight, eps)
     q = ref.apply_rope(q, cos, sin)
     k = ref.apply_rope(k, cos, sin)
     return q.reshape(T, hq * d), k.reshape(T, hkv * d), v

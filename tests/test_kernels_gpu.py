@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 from llm_in_practise_amd.ops import reference as ref
 from llm_in_practise_amd.quant.nf4 import dequantize_nf4, quantize_nf4
+from oracle import assert_close_ulp
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -38,6 +39,13 @@ def test_rmsnorm_fwd_bwd(native_ext, M, N):
     yr.backward(dy.float())
     assert rel_err(dx, xr.grad) < 1e-2
     assert rel_err(dw, wr.grad) < 1e-2
+    # every element against fp64 (tests/oracle.py)
+    y64, r64 = ref.rmsnorm_fwd64(x, w, 1e-6)
+    dx64, s_dx, dw64, s_dw = ref.rmsnorm_bwd64(dy, x, w, 1e-6)
+    assert_close_ulp(y, y64, name=f"rmsnorm {M}x{N} y")
+    assert_close_ulp(rstd, r64, name=f"rmsnorm {M}x{N} rstd")
+    assert_close_ulp(dx, dx64, s_dx, name=f"rmsnorm {M}x{N} dx")
+    assert_close_ulp(dw, dw64, s_dw, name=f"rmsnorm {M}x{N} dw")
 
 
 @pytest.mark.parametrize("M,N", [(2048, 4096), (37, 4096), (5, 1024), (300, 2048), (64, 8192)])
@@ -55,6 +63,11 @@ def test_rmsnorm_split_rows(native_ext, M, N):
     dx, _ = native_ext.rmsnorm_bwd(dy, x, w, rstd, False, dres)
     yr.backward(dy.float())
     assert rel_err(dx, xr.grad + dres.float()) < 1e-2
+    y64, r64 = ref.rmsnorm_fwd64(x, w, 1e-6)
+    dx64, s_dx, _, _ = ref.rmsnorm_bwd64(dy, x, w, 1e-6, dres)
+    assert_close_ulp(y, y64, name=f"rmsnorm split {M}x{N} y")
+    assert_close_ulp(rstd, r64, name=f"rmsnorm split {M}x{N} rstd")
+    assert_close_ulp(dx, dx64, s_dx, name=f"rmsnorm split {M}x{N} dx")
 
 
 def test_rmsnorm_residual_fn(native_ext):
@@ -72,6 +85,9 @@ def test_rmsnorm_residual_fn(native_ext):
     ((yr * g1.float()).sum() + (xr * g2.float()).sum()).backward()
     assert rel_err(x.grad, xr.grad) < 1e-2
     assert rel_err(w.grad, wr.grad) < 1e-2
+    dx64, s_dx, dw64, s_dw = ref.rmsnorm_bwd64(g1, x, w, 1e-6, g2)
+    assert_close_ulp(x.grad, dx64, s_dx, name="rmsnorm residual dx")
+    assert_close_ulp(w.grad, dw64, s_dw, name="rmsnorm residual dw")      # the fp32 column sum rounded to bf16
 
 
 @pytest.mark.parametrize("M,N", [(512, 768), (33, 1024), (16, 64)])
@@ -89,6 +105,14 @@ def test_layernorm_fwd_bwd(native_ext, M, N):
     assert rel_err(dx, xr.grad) < 2e-2
     assert rel_err(dw, wr.grad) < 1e-2
     assert rel_err(db, br.grad) < 1e-2
+    y64, s_y, mu64, r64 = ref.layernorm_fwd64(x, w, b, 1e-5)
+    dx64, s_dx, dw64, s_dw, db64, s_db = ref.layernorm_bwd64(dy, x, w, 1e-5)
+    assert_close_ulp(y, y64, s_y, name=f"layernorm {M}x{N} y")
+    assert_close_ulp(mean, mu64, x.double().abs().mean(-1), name=f"layernorm {M}x{N} mean")
+    assert_close_ulp(rstd, r64, name=f"layernorm {M}x{N} rstd")
+    assert_close_ulp(dx, dx64, s_dx, name=f"layernorm {M}x{N} dx")
+    assert_close_ulp(dw, dw64, s_dw, name=f"layernorm {M}x{N} dw")
+    assert_close_ulp(db, db64, s_db, name=f"layernorm {M}x{N} db")
 
 
 # ----------------------------------------------------------------------------- rope
@@ -118,6 +142,12 @@ def test_qk_norm_rope(native_ext, hq, hkv, d):
     g = x.grad.clone()
     g[:, (hq + hkv) * d:] = dv.float()
     assert rel_err(dqkv, g) < 2e-2
+    # per element: the operand term of q / k is 2^-7·S, one bf16 ulp of the normed value that is rounded before
+    # the rotation (where the kernel's fp32 value and the reference's fp64 value round apart)
+    (q64, s_q, k64, s_k), g64, s_g = ref.qk_norm_rope64(qkv, qw, kw, cos, sin, hq, hkv, d, 1e-6, dq, dk)
+    assert_close_ulp(q, q64, s_q * 2.0 ** 9, name=f"qk_norm_rope d={d} q")
+    assert_close_ulp(k, k64, s_k * 2.0 ** 9, name=f"qk_norm_rope d={d} k")
+    assert_close_ulp(dqkv[:, :(hq + hkv) * d], g64, s_g, name=f"qk_norm_rope d={d} dqkv")
     assert torch.equal(dqkv[:, (hq + hkv) * d:], dv)          # v rows pass through exactly
     d0 = native_ext.qk_norm_rope_bwd(dq, dk, None, qkv, qw, kw, cos, sin, rq, rk, hq, hkv, d)
     assert torch.equal(d0[:, :(hq + hkv) * d], dqkv[:, :(hq + hkv) * d])
@@ -145,6 +175,9 @@ def test_swiglu(native_ext):
     dy = torch.randn_like(y)
     yr.backward(dy.float())
     assert rel_err(native_ext.swiglu_bwd(dy, gu), x.grad) < 1e-2
+    g64, s_g = ref.swiglu_bwd64(dy, gu)
+    assert_close_ulp(y, ref.swiglu_fwd64(gu), name="swiglu y")
+    assert_close_ulp(native_ext.swiglu_bwd(dy, gu), g64, s_g, name="swiglu dgu")
 
 
 def test_gelu(native_ext):
@@ -155,6 +188,10 @@ def test_gelu(native_ext):
     dy = torch.randn_like(x)
     yr.backward(dy.float())
     assert rel_err(native_ext.gelu_bwd(dy, x), xr.grad) < 1e-2
+    y64, s_y = ref.gelu_fwd64(x)
+    dx64, s_dx = ref.gelu_bwd64(dy, x)
+    assert_close_ulp(native_ext.gelu_fwd(x), y64, s_y, name="gelu y")
+    assert_close_ulp(native_ext.gelu_bwd(dy, x), dx64, s_dx, name="gelu dx")
 
 
 @pytest.mark.parametrize("V", [151936, 512])
@@ -171,6 +208,12 @@ def test_cross_entropy(native_ext, V):
     rows = native_ext.ce_fwd_bwd(lg, labels, -100, (1.0 / n_valid.float()).reshape(1))
     assert abs(rows.sum().item() / n_valid.item() - loss_ref.item()) < 1e-3 * max(1, loss_ref.item())
     assert rel_err(lg, lf.grad) < 2e-2
+    inv = (1.0 / n_valid.float()).reshape(1)                # the fp32 scale the kernel read
+    loss64, g64, s_g = ref.ce_fwd_bwd64(logits, labels, -100, inv.expand(M))
+    xd = logits.double()
+    s_loss = torch.logsumexp(xd, -1).abs() + xd.gather(1, labels.clamp_min(0)[:, None]).squeeze(1).abs()
+    assert_close_ulp(rows, loss64, s_loss * (labels != -100), name=f"ce V={V} loss")
+    assert_close_ulp(lg, g64, s_g, name=f"ce V={V} dlogits")
 
 
 @pytest.mark.parametrize("groups", [1, 2])

@@ -7,7 +7,7 @@
     lipa chat --base DIR [--adapter DIR]                                        (E8, G1, G2)
     lipa merge --base DIR --adapter DIR --out DIR                               (E10 export, E11 02/04, K19)
     lipa quantize --method {gptq,awq,rtn} --model DIR --out DIR [--format ...]  (F1-F4)
-    lipa eval-quant --model DIR                                                  (F2b)
+    lipa eval-quant --model DIR [--engine]                                       (F2b)
     lipa infer --model DIR --prompt TEXT                                        (F1b, F2c, G1)
     lipa serve --model DIR [--adapter DIR] [--port 8000]                        (G4, H1)
                [--enable-lora --lora-modules n1=dir1 n2=dir2] [--kv-host-cache-blocks N]
@@ -426,6 +426,19 @@ def cmd_eval_quant(a):
         prompts = [torch.tensor(tok.encode(t)[:256], device=dev) for t in load_text_corpus(a.prompts)[a.start:a.end]]
     else:
         prompts = [torch.randint(0, m.config.vocab_size, (32,), device=dev) for _ in range(a.end - a.start)]
+    if a.engine:       # the reference's figure through the serving engine (batched decode, token log-probabilities)
+        from ..infer.engine import ServingEngine
+        from ..quant.eval import self_ppl_engine
+        from ..train.data import ByteTokenizer
+        eng = ServingEngine(m, tok if tok is not None else ByteTokenizer(), max_batch=max(1, min(len(prompts), 64)),
+                            max_model_len=a.max_model_len)
+        try:
+            mean, std = self_ppl_engine(eng, prompts, a.max_new)
+        finally:
+            eng.shutdown()
+        print(json.dumps({"self_ppl_mean": mean, "self_ppl_std": std, "pass": mean < PASS_THRESHOLD,
+                          "threshold": PASS_THRESHOLD}))
+        return
     ppl = self_ppl(m, prompts, a.max_new, getattr(tok, "eos_token_id", None))
     print(json.dumps({"self_ppl": ppl, "pass": ppl < PASS_THRESHOLD, "threshold": PASS_THRESHOLD}))
 
@@ -550,7 +563,7 @@ def cmd_serve(a):
             eng.follower_loop()              # TP / PP followers replay rank 0's iterations
             return
     serve(eng, a.host, a.port, api_key=a.api_key, moderation=moderation,
-          log_level=getattr(a, "uvicorn_log_level", "info"))
+          max_logprobs=min(20, max(0, getattr(a, "max_logprobs", 20))), log_level=getattr(a, "uvicorn_log_level", "info"))
 
 
 def cmd_serve_deploy(a):
@@ -976,6 +989,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--start", type=int, default=128)
     p.add_argument("--end", type=int, default=256)
     p.add_argument("--max_new", type=int, default=256)
+    p.add_argument("--engine", action="store_true",
+                   help="generate through the serving engine with logprobs=1 (the reference's vLLM evaluation): "
+                        "prints self_ppl_mean / self_ppl_std over the prompts")
+    p.add_argument("--max-model-len", dest="max_model_len", type=int, default=None)
     p.set_defaults(fn=cmd_eval_quant)
 
     p = sub.add_parser("serve", help="OpenAI-compatible server; also takes vLLM's `vllm serve` flags (_vllm_compat)")
@@ -1008,6 +1025,8 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument(flag, action="store_true", help="accepted for vLLM compatibility (no effect)")
     p.add_argument("--served-model-name", dest="served_model_name")
     p.add_argument("--api-key", dest="api_key")
+    p.add_argument("--max-logprobs", dest="max_logprobs", type=int, default=20,
+                   help="vLLM flag: most log-probabilities per token a request may ask for (HTTP 400 above it)")
     p.add_argument("--guard-url", dest="guard_url")
     p.add_argument("--system", default=None)
     p.add_argument("--enable-prefix-caching", dest="prefix_caching", action="store_true",

@@ -131,6 +131,8 @@ void launch_decode_attention2(const void*, int, const void*, int, const void*, i
                               float*, float*, void*, int, int, int, int, int, int, float, hipStream_t);
 void launch_sample(int, const void*, const int*, int, float*, int64_t*, int, int, float, int, float, float, uint64_t,
                    hipStream_t);
+void launch_sample_logprobs(int, const void*, const int*, int, float*, int64_t*, float*, int64_t*, float*, int, int, int,
+                            float, int, float, float, uint64_t, hipStream_t);
 void* car_alloc(size_t, bool);
 void car_free(void*);
 bool car_ipc_handle(void*, char*);
@@ -1720,6 +1722,39 @@ Tensor sample(Tensor logits, optional<Tensor> hist, double temperature, int64_t 
   return out;
 }
 
+// sample() plus raw log-probabilities lp_i = x_i - logsumexp(x) (penalty / temperature / top-k / top-p do not
+// enter): (tokens [B] int64, lp [B] fp32, top_id [B, num_top] int64, top_lp [B, num_top] fp32); the top entries
+// are ordered by value descending, lowest id first among equals
+std::vector<Tensor> sample_logprobs(Tensor logits, optional<Tensor> hist, double temperature, int64_t top_k,
+                                    double top_p, double penalty, int64_t num_top, int64_t key) {
+  CHECK_CUDA(logits);
+  CHECK_CONTIG(logits);
+  dtype_code(logits);
+  TORCH_CHECK(logits.dim() == 2, "sample_logprobs: logits [B, V]");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V > 0 && V <= INT_MAX && B <= INT_MAX, "sample_logprobs: logits shape");
+  TORCH_CHECK(num_top >= 0 && num_top <= 20 && num_top <= V, "sample_logprobs: num_top ", num_top,
+              " outside [0, min(20, V = ", V, ")]");
+  int L = 0;
+  if (hist.has_value() && hist->defined()) {
+    TORCH_CHECK(hist->is_cuda() && hist->scalar_type() == at::kInt && hist->is_contiguous() && hist->dim() == 2 &&
+                    hist->size(0) == B,
+                "hist: [B,L] int32");
+    L = hist->size(1);
+  }
+  Tensor work = at::empty({B, V}, logits.options().dtype(at::kFloat));
+  Tensor out = at::empty({B}, logits.options().dtype(at::kLong));
+  Tensor lp = at::empty({B}, logits.options().dtype(at::kFloat));
+  Tensor top_id = at::empty({B, num_top}, logits.options().dtype(at::kLong));
+  Tensor top_lp = at::empty({B, num_top}, logits.options().dtype(at::kFloat));
+  if (B > 0)
+    launch_sample_logprobs(dtype_code(logits), logits.data_ptr(), L ? hist->data_ptr<int>() : nullptr, L,
+                           work.data_ptr<float>(), out.data_ptr<int64_t>(), lp.data_ptr<float>(),
+                           top_id.data_ptr<int64_t>(), top_lp.data_ptr<float>(), (int)num_top, B, V, (float)temperature,
+                           (int)top_k, (float)top_p, (float)penalty, (uint64_t)key, stream());
+  return {out, lp, top_id, top_lp};
+}
+
 }  // namespace
 
 
@@ -1887,6 +1922,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_apply", &lora_apply);
   m.def("gemv_w4", &gemv_w4);
   m.def("sample", &sample);
+  m.def("sample_logprobs", &sample_logprobs);
   m.def("adamw", &adamw);
   m.def("adamw8bit", &adamw8bit);
   m.def("host_mapped_empty", &host_mapped_empty, py::arg("numel"), py::arg("dtype"));

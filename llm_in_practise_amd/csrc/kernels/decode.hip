@@ -18,6 +18,9 @@
 // per distinct history token), temperature, top-k and top-p by value-threshold bisection over
 // the row (no sort of the 151,936-entry vocabulary), then an inverse-CDF draw from a
 // counter-based RNG (splitmix64 of (key, row)) with a block prefix scan.  Greedy = argmax.
+// The log-probability variant (sample_k<T, true>) picks the token in exactly the same way and adds
+// an epilogue over the RAW row: lp_i = x_i - logsumexp(x) of the chosen token and of the N most
+// likely tokens, ordered by (value descending, id ascending).
 #include "common.h"
 
 #include <algorithm>
@@ -385,14 +388,93 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
 
 __device__ __forceinline__ float bsum(float v, float* red) { return block_sum<SMP_NW>(v, red); }
 
+// Outputs of the log-probability variant: lp [B], top_id / top_lp [B, num_top].
+struct SampleLp {
+  float* lp;
+  int64_t* top_id;
+  float* top_lp;
+  int num_top;
+};
+
+// (value descending, id ascending): does (v, i) come before (bv, bi)?
+__device__ __forceinline__ bool lp_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+__device__ __forceinline__ void lp_wave_best(float& v, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (lp_before(ov, oi, v, i)) { v = ov; i = oi; }
+  }
+}
+
+// Epilogue of sample_k<T, true>, called by the whole workgroup once the token `tok` of the row is known.
+// Raw log-probabilities: its own max and sum over x, whatever penalty / temperature / top-k / top-p did
+// to the row the token was drawn from.  Top-N: every thread holds the best not yet extracted element of its
+// strided share (tid, tid + 1024, ...); each of the N rounds takes the block's best candidate, and the
+// wave that owned it rescans the owner's share (<= V/1024 elements spread over 64 lanes) for the next one.
 template <typename T>
+__device__ void sample_logprobs_epilogue(const T* __restrict__ x, int V, int row, int tok, const SampleLp& o,
+                                         int64_t* __restrict__ out, float* red) {
+  __shared__ float cand_v[2][SMP_NW];
+  __shared__ int cand_i[2][SMP_NW];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  float cv = -INFINITY;
+  int ci = 0x7FFFFFFF;           // no candidate: sorts after every element, -inf ones included
+  for (int i = tid; i < V; i += SMP_THR) {
+    const float v = (float)x[i];
+    if (lp_before(v, i, cv, ci)) { cv = v; ci = i; }
+  }
+  const float m = block_max<SMP_NW>(cv, red);
+  float sum = 0.f;
+  for (int i = tid; i < V; i += SMP_THR) sum += expf((float)x[i] - m);
+  sum = bsum(sum, red);
+  const float lse = logf(sum);
+  auto lp_of = [&](float v) { return v == -INFINITY ? -INFINITY : (v - m) - lse; };
+  if (tid == 0) {
+    out[row] = tok;
+    o.lp[row] = tok >= 0 && tok < V ? lp_of((float)x[tok]) : NAN;   // (an all-NaN row has no argmax)
+  }
+  for (int r = 0; r < o.num_top; ++r) {
+    float bv = cv;
+    int bi = ci;
+    lp_wave_best(bv, bi);
+    if (lane == 0) { cand_v[r & 1][w] = bv; cand_i[r & 1][w] = bi; }
+    __syncthreads();             // the other buffer is rewritten only after the next round's barrier
+    bv = cand_v[r & 1][0];
+    bi = cand_i[r & 1][0];
+#pragma unroll
+    for (int j = 1; j < SMP_NW; ++j)
+      if (lp_before(cand_v[r & 1][j], cand_i[r & 1][j], bv, bi)) { bv = cand_v[r & 1][j]; bi = cand_i[r & 1][j]; }
+    if (tid == 0) {
+      o.top_id[(size_t)row * o.num_top + r] = bi;
+      o.top_lp[(size_t)row * o.num_top + r] = lp_of(bv);
+    }
+    const int owner = bi & (SMP_THR - 1);      // num_top <= V: bi is a real index in every round
+    if ((owner >> 6) == w) {
+      float nv = -INFINITY;
+      int ni = 0x7FFFFFFF;
+      const int cnt = (V - owner + SMP_THR - 1) / SMP_THR;   // elements of the owner's share
+      for (int k = lane; k < cnt; k += 64) {
+        const int i = owner + k * SMP_THR;
+        const float v = (float)x[i];
+        if (lp_before(bv, bi, v, i) && lp_before(v, i, nv, ni)) { nv = v; ni = i; }
+      }
+      lp_wave_best(nv, ni);
+      if (lane == (owner & 63)) { cv = nv; ci = ni; }
+    }
+  }
+}
+
+template <typename T, bool LP = false>
 __global__ __launch_bounds__(SMP_THR) void sample_k(const T* __restrict__ logits, const int* __restrict__ hist,
                                                     int hist_len, float* __restrict__ work, int64_t* __restrict__ out,
                                                     int V, float temperature, int top_k, float top_p, float penalty,
-                                                    uint64_t key) {
+                                                    uint64_t key, SampleLp lpo = SampleLp{}) {
   __shared__ float red[SMP_NW];
   __shared__ float sc[SMP_THR];
   __shared__ int si[SMP_NW];
+  __shared__ int s_pick;
   const int row = blockIdx.x, tid = threadIdx.x;
   const T* x = logits + (size_t)row * V;
   float* wv = work + (size_t)row * V;
@@ -429,8 +511,15 @@ __global__ __launch_bounds__(SMP_THR) void sample_k(const T* __restrict__ logits
     if (red[i] > best || (red[i] == best && si[i] < bidx)) { best = red[i]; bidx = si[i]; }
   __syncthreads();
   if (!(temperature > 0.f)) {  // greedy
-    if (tid == 0) out[row] = bidx;
+    if constexpr (LP) {
+      sample_logprobs_epilogue(x, V, row, bidx, lpo, out, red);
+    } else {
+      if (tid == 0) out[row] = bidx;
+    }
     return;
+  }
+  if constexpr (LP) {
+    if (tid == 0) s_pick = bidx;   // ordered before the pick below by the barriers of the scan
   }
   const float invT = 1.f / temperature;
   const float mx = best * invT;
@@ -491,9 +580,15 @@ __global__ __launch_bounds__(SMP_THR) void sample_k(const T* __restrict__ logits
       run += p;
       if (u < run) { pick = i; break; }
     }
-    out[row] = pick;
+    if constexpr (LP) s_pick = pick; else out[row] = pick;
   }
-  if (tid == 0 && !(total > 0.f)) out[row] = bidx;
+  if constexpr (LP) {
+    // (total <= 0 leaves s_pick = bidx, as below)  the pick was written by one thread: make it visible
+    __syncthreads();
+    sample_logprobs_epilogue(x, V, row, s_pick, lpo, out, red);
+  } else {
+    if (tid == 0 && !(total > 0.f)) out[row] = bidx;
+  }
 }
 
 }  // namespace
@@ -566,5 +661,19 @@ void launch_sample(int dtype, const void* logits, const int* hist, int hist_len,
   else
     sample_k<bf16><<<B, SMP_THR, 0, st>>>((const bf16*)logits, hist, hist_len, work, out, V, temperature, top_k,
                                           top_p, penalty, key);
+  LIPA_CHECK_LAUNCH();
+}
+
+// The sampler plus raw log-probabilities: lp [B], top_id / top_lp [B, num_top] (0 <= num_top <= V).
+void launch_sample_logprobs(int dtype, const void* logits, const int* hist, int hist_len, float* work, int64_t* out,
+                            float* lp, int64_t* top_id, float* top_lp, int num_top, int B, int V, float temperature,
+                            int top_k, float top_p, float penalty, uint64_t key, hipStream_t st) {
+  const SampleLp o{lp, top_id, top_lp, num_top};
+  if (dtype == 0)
+    sample_k<float, true><<<B, SMP_THR, 0, st>>>((const float*)logits, hist, hist_len, work, out, V, temperature,
+                                                 top_k, top_p, penalty, key, o);
+  else
+    sample_k<bf16, true><<<B, SMP_THR, 0, st>>>((const bf16*)logits, hist, hist_len, work, out, V, temperature,
+                                                top_k, top_p, penalty, key, o);
   LIPA_CHECK_LAUNCH();
 }

@@ -32,7 +32,7 @@ from typing import Any
 import torch
 
 from ..models.common import KVCache, PackedPrefill
-from ..ops.decode import sample
+from ..ops.decode import MAX_LOGPROBS, sample, sample_logprobs
 from ..ops.linear import head_logits
 from ..train.data import render_chatml
 
@@ -46,9 +46,22 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     stop: list[str] | None = None
     ignore_eos: bool = False            # vLLM extra param (``vllm bench serve --ignore-eos``)
+    # vLLM ``SamplingParams.logprobs``: None = off, 0 = the sampled token's raw log-probability only,
+    # k in 1..20 = plus the k most likely tokens of the raw distribution (ops.decode.sample_logprobs)
+    logprobs: int | None = None
 
     def key(self):
         return (self.temperature, self.top_p, self.top_k, self.repetition_penalty)
+
+
+class Delta(str):
+    """A streamed text piece that also carries the log-probability entries of the tokens whose text it
+    emits (``("delta", Delta)`` items of requests with ``logprobs``; every consumer of the text sees a str)."""
+
+    def __new__(cls, text: str = "", logprobs: list | None = None):
+        o = super().__new__(cls, text)
+        o.logprobs = logprobs
+        return o
 
 
 @dataclasses.dataclass
@@ -287,6 +300,13 @@ class _Slot:
     prefilled: int = -1                  # chunked prefill: prompt tokens in the cache so far (-1 = decoding)
     done: bool = False
     finish: str = "length"
+    lps: list | None = None              # one entry per sampled token (a terminating EOS included), if asked for
+    lp_sent: int = 0                     # entries already streamed
+    eos_tok: int | None = None           # the EOS token the request ended on (not part of gen)
+
+    def __post_init__(self):
+        if self.req.params.logprobs is not None:
+            self.lps = []
 
 
 class _Histogram:
@@ -515,8 +535,12 @@ class ServingEngine:
         """``out``: any object with a thread-safe ``put`` (default a ``queue.Queue``); the HTTP server
         passes an :class:`AsyncOut` so streamed deltas reach its event loop without a thread hop
         per token."""
+        k = params.logprobs
+        if k is not None and not 0 <= k <= min(MAX_LOGPROBS, self.lm.lm_head.weight.shape[0]):
+            raise ValueError(f"logprobs {k}: must be None or in 0..{MAX_LOGPROBS}")
         room = self.max_len - 1 - min(params.max_tokens, self.max_len // 2)   # keep space to generate
-        ids = self.encode(prompt)[-room:]
+        # (a prompt given as token ids is taken as it is: quant/eval.py self_ppl_engine)
+        ids = (self.encode(prompt) if isinstance(prompt, str) else [int(t) for t in prompt])[-room:]
         r = _Request(ids, params, stream, out if out is not None else queue.Queue(), time.time(),
                      adapter=self.adapter_id(model))
         self.q.put(r)
@@ -727,11 +751,11 @@ class ServingEngine:
         s.prefilled = -1
         self.stats["prompt_tokens_total"] += L
         logits = head_logits(h[-1:], self.lm.lm_head.weight)
-        dev_toks, toks = self._sample(logits, [slot])
+        dev_toks, toks, ents = self._sample(logits, [slot])
         self.next_tok[slot] = dev_toks[0]
         if self.prefix is not None:
             self.prefix.store(r.prompt_ids, self.cache, slot, self._salt(r.adapter))
-        self._accept(slot, toks[0], time.time())
+        self._accept(slot, toks[0], time.time(), ents[0])
 
     def _admit_suffix(self, slot, r, idx):
         lm = self.lm
@@ -749,9 +773,9 @@ class ServingEngine:
         self.cache.pos[slot] = L
         self.slots[slot] = _Slot(r)
         self.stats["prompt_tokens_total"] += L
-        dev_toks, toks = self._sample(logits, [slot])
+        dev_toks, toks, ents = self._sample(logits, [slot])
         self.next_tok[slot] = dev_toks[0]
-        self._accept(slot, toks[0], time.time())
+        self._accept(slot, toks[0], time.time(), ents[0])
         self.stats["batches_total"] += 1
 
     def _admit_batch(self, new):
@@ -773,20 +797,57 @@ class ServingEngine:
         for b, (slot, r) in enumerate(new):
             self.slots[slot] = _Slot(r)
             self.stats["prompt_tokens_total"] += len(r.prompt_ids)
-        dev_toks, toks = self._sample(logits, [s for s, _ in new])
+        dev_toks, toks, ents = self._sample(logits, [s for s, _ in new])
         self.next_tok[rows] = dev_toks
         for b, (slot, r) in enumerate(new):
-            self._accept(slot, toks[b], now)
+            self._accept(slot, toks[b], now, ents[b])
         self.stats["batches_total"] += 1
 
     def _sample(self, logits, slot_ids):
         """Sample one token per row, grouping rows with identical sampling parameters.
-        Returns (device tensor, host list)."""
-        out = self._sample_dev(logits, slot_ids)
-        return out, out.tolist()
+        Returns (device tensor, host list, per-row log-probability entries — None for a row that asked
+        for none)."""
+        out, lpt = self._sample_dev(logits, slot_ids)
+        if lpt is None:
+            return out, out.tolist(), [None] * len(slot_ids)
+        toks, ents = self._lp_entries(self._lp_pack(out, lpt).cpu(),
+                                      [self.slots[s].req.params.logprobs for s in slot_ids])
+        return out, toks, ents
+
+    @staticmethod
+    def _lp_pack(toks, lpt):
+        """Tokens and their log-probability tensors as ONE int32 tensor [n, 2 + 2N] (token, lp bits, top ids,
+        top lp bits), so that they reach the host in one copy."""
+        lp, top_id, top_lp = lpt
+        return torch.cat([toks.to(torch.int32)[:, None], lp.view(torch.int32)[:, None], top_id.to(torch.int32),
+                          top_lp.view(torch.int32)], 1)
+
+    @staticmethod
+    def _lp_entries(host, want):
+        """Host side of :meth:`_lp_pack` -> (token list, entries): ``{"id", "logprob", "top": [(id, logprob)]}``
+        cut to the ``want[row]`` top entries the row's request asked for, None where it asked for none."""
+        N = (host.shape[1] - 2) // 2
+        toks = host[:, 0].tolist()
+        lp = host[:, 1].contiguous().view(torch.float32).tolist()
+        tid = host[:, 2:2 + N].tolist()
+        tlp = host[:, 2 + N:].contiguous().view(torch.float32).tolist()
+        ents = [None if k is None else {"id": toks[j], "logprob": lp[j], "top": list(zip(tid[j][:k], tlp[j][:k]))}
+                for j, k in enumerate(want)]
+        return toks, ents
 
     def _sample_dev(self, logits, slot_ids):
+        """-> (tokens, None), or (tokens, (lp [n], top_id [n, N], top_lp [n, N])) when a row asks for
+        log-probabilities (N = the largest request; a group of rows in which nobody asks runs plain
+        ``sample``, so a step without such requests launches exactly what it always did)."""
         out = torch.empty(len(slot_ids), dtype=torch.long, device=self.device)
+        want = [self.slots[s].req.params.logprobs for s in slot_ids]
+        nmax = max((k for k in want if k is not None), default=None)
+        lpt = None
+        if nmax is not None:
+            n = len(slot_ids)
+            lpt = (torch.zeros(n, dtype=torch.float32, device=self.device),
+                   torch.zeros(n, nmax, dtype=torch.long, device=self.device),
+                   torch.zeros(n, nmax, dtype=torch.float32, device=self.device))
         groups: dict = {}
         for j, s in enumerate(slot_ids):
             groups.setdefault(self.slots[s].req.params.key(), []).append(j)
@@ -801,19 +862,33 @@ class ServingEngine:
                     seq = s.req.prompt_ids + s.gen
                     hist[q, :len(seq)] = torch.tensor(seq, dtype=torch.int32)
                 hist = hist.to(self.device)
-            if idx is None:
+            k = max((want[j] for j in js if want[j] is not None), default=None)
+            if k is not None:
+                x = logits.float() if idx is None else logits[idx].float()
+                t, lp, top_id, top_lp = sample_logprobs(x, hist, temp, top_k, top_p, pen, num_top=k)
+                rows = slice(None) if idx is None else idx
+                lpt[0][rows] = lp
+                lpt[1][rows, :k] = top_id
+                lpt[2][rows, :k] = top_lp
+                if idx is None:
+                    out = t
+                else:
+                    out[idx] = t
+            elif idx is None:
                 out = sample(logits.float(), hist, temp, top_k, top_p, pen)
             else:
                 out[idx] = sample(logits[idx].float(), hist, temp, top_k, top_p, pen)
-        return out
+        return out, lpt
 
-    def _accept(self, slot: int, tok: int, now: float):
+    def _accept(self, slot: int, tok: int, now: float, entry: dict | None = None):
         s = self.slots[slot]
         if s.t_first is None:
             s.t_first = now
         p = s.req.params
+        if s.lps is not None:
+            s.lps.append(entry)            # every sampled token, a terminating EOS included (as vLLM)
         if tok in self.eos and not p.ignore_eos:
-            s.done, s.finish = True, "stop"
+            s.done, s.finish, s.eos_tok = True, "stop", tok
         else:
             s.gen.append(tok)
             if len(s.gen) >= p.max_tokens or len(s.req.prompt_ids) + len(s.gen) >= self.max_len - 1:
@@ -828,6 +903,9 @@ class ServingEngine:
                     s.poff, s.roff = s.roff, len(s.gen)
                     s.text += new
                     if s.req.stream:
+                        if s.lps is not None:      # the entries of the tokens this piece emits (held-back ones too)
+                            new = Delta(new, s.lps[s.lp_sent:])
+                            s.lp_sent = len(s.lps)
                         s.req.out.put(("delta", new))
                         s.sent = len(s.text)
                     if p.stop:
@@ -846,7 +924,13 @@ class ServingEngine:
             if cut >= 0:
                 text = text[:cut]
         if r.stream and len(text) > len(s.text) and text.startswith(s.text):
-            r.out.put(("delta", text[len(s.text):]))       # flush a held-back partial character
+            tail = text[len(s.text):]                       # flush a held-back partial character
+            if s.lps is not None:
+                tail = Delta(tail, s.lps[s.lp_sent:])
+                s.lp_sent = len(s.lps)
+            r.out.put(("delta", tail))
+        if r.stream and s.lps is not None and s.lp_sent < len(s.lps):
+            r.out.put(("delta", Delta("", s.lps[s.lp_sent:])))   # entries without text of their own (EOS)
         t1 = time.time()
         self.stats["requests_total"] += 1
         self.stats["generation_tokens_total"] += len(s.gen)
@@ -855,7 +939,9 @@ class ServingEngine:
             self.h_ttft.observe(s.t_first - r.t_arrive)
         r.out.put(("final", {"text": text, "finish_reason": s.finish, "prompt_tokens": len(r.prompt_ids),
                              "completion_tokens": len(s.gen), "latency_s": t1 - r.t_arrive,
-                             "ttft_s": (s.t_first or t1) - r.t_arrive}))
+                             "ttft_s": (s.t_first or t1) - r.t_arrive,
+                             "token_ids": s.gen + ([s.eos_tok] if s.eos_tok is not None else []),
+                             "logprobs": s.lps}))
         self.slots[slot] = None
         self.cache.pos[slot] = 0
 
@@ -885,10 +971,15 @@ class ServingEngine:
             # copy + event hand them to the host, and the host accepts the PREVIOUS step's
             # tokens while this step runs on the GPU (a finished request decodes one extra,
             # discarded token)
-            dev_toks = self._sample_dev(logits, active)
+            dev_toks, lpt = self._sample_dev(logits, active)
             self.next_tok[rows] = dev_toks
-            host = torch.empty(len(active), dtype=torch.long, pin_memory=True)
-            host.copy_(dev_toks, non_blocking=True)
+            if lpt is None:
+                host = torch.empty(len(active), dtype=torch.long, pin_memory=True)
+                host.copy_(dev_toks, non_blocking=True)
+            else:                    # the log-probabilities ride with the tokens: one packed pinned copy
+                packed = self._lp_pack(dev_toks, lpt)
+                host = torch.empty(packed.shape, dtype=torch.int32, pin_memory=True)
+                host.copy_(packed, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             prev, self._pending = self._pending, (host, ev, [(sl, self.slots[sl].req) for sl in active])
@@ -896,11 +987,11 @@ class ServingEngine:
                 self._process_pending(prev)
         else:
             self._flush_pending()
-            dev_toks, toks = self._sample(logits, active)
+            dev_toks, toks, ents = self._sample(logits, active)
             self.next_tok[rows] = dev_toks
             now = time.time()
             for j, slot in enumerate(active):
-                self._accept(slot, toks[j], now)
+                self._accept(slot, toks[j], now, ents[j])
         self.stats["decode_steps_total"] += 1
         self.stats["running"] = sum(s is not None for s in self.slots)
 
@@ -908,10 +999,14 @@ class ServingEngine:
         host, ev, owners = pend
         ev.synchronize()
         now = time.time()
-        for (slot, req), tok in zip(owners, host.tolist()):
+        if host.dim() == 1:
+            toks, ents = host.tolist(), [None] * len(owners)
+        else:                        # packed tokens + log-probabilities (_lp_pack)
+            toks, ents = self._lp_entries(host, [req.params.logprobs for _, req in owners])
+        for (slot, req), tok, ent in zip(owners, toks, ents):
             s = self.slots[slot]
             if s is not None and s.req is req and not s.done:
-                self._accept(slot, tok, now)
+                self._accept(slot, tok, now, ent)
 
     def _flush_pending(self):
         if self._pending is not None:

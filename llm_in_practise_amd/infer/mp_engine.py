@@ -13,7 +13,10 @@ to the frontend as ONE batched message over a pipe:
 
 The client implements the subset of :class:`~.engine.ServingEngine` the server uses
 (``submit`` / ``complete`` / ``stream`` / ``build_chat_prompt`` / ``prometheus`` / names), so
-``create_app(EngineClient(...))`` serves exactly like the in-process engine.
+``create_app(EngineClient(...))`` serves exactly like the in-process engine.  Token log-probabilities
+cross the pipe as they are: ``SamplingParams.logprobs`` inside the submitted parameter dict, the entries
+on the pickled :class:`~.engine.Delta` pieces and in the ``"final"`` result (``token_ids``, ``logprobs``);
+the frontend turns ids into token texts with the formatter's tokenizer.
 """
 from __future__ import annotations
 

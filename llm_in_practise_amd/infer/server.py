@@ -47,6 +47,8 @@ class ChatCompletionRequest(BaseModel):
     stream: bool = False
     stop: Optional[Union[str, list[str]]] = None
     ignore_eos: bool = False
+    logprobs: bool = False
+    top_logprobs: Optional[int] = Field(None, ge=0)      # needs logprobs; capped by --max-logprobs (400 above it)
 
 
 class CompletionRequest(BaseModel):
@@ -60,6 +62,7 @@ class CompletionRequest(BaseModel):
     stream: bool = False
     stop: Optional[Union[str, list[str]]] = None
     ignore_eos: bool = False
+    logprobs: Optional[int] = Field(None, ge=0)          # capped by --max-logprobs (400 above it)
 
 
 class ChoiceMessage(BaseModel):
@@ -88,16 +91,68 @@ class ChatCompletionResponse(BaseModel):
     usage: Usage
 
 
-def _params(req) -> SamplingParams:
+def _params(req, max_logprobs: int = 20) -> SamplingParams:
     stop = [req.stop] if isinstance(req.stop, str) else req.stop
+    if isinstance(req, ChatCompletionRequest):
+        if req.top_logprobs is not None and not req.logprobs:
+            raise HTTPException(status_code=400, detail="top_logprobs requires logprobs to be true")
+        k = (req.top_logprobs or 0) if req.logprobs else None
+    else:
+        k = req.logprobs
+    if k is not None and k > max_logprobs:        # vLLM --max-logprobs: refused, not clamped
+        raise HTTPException(status_code=400, detail=f"{k} logprobs requested, at most {max_logprobs} are served")
     return SamplingParams(max_tokens=req.max_tokens, temperature=req.temperature, top_p=req.top_p, top_k=req.top_k,
                           repetition_penalty=req.repetition_penalty, stop=stop,
-                          ignore_eos=req.ignore_eos)
+                          ignore_eos=req.ignore_eos, logprobs=k)
 
 
-def create_app(engine: ServingEngine, api_key: str | None = None, moderation=None) -> FastAPI:
+def _tokenizer(engine):
+    tok = getattr(engine, "tok", None)
+    return tok if tok is not None else engine.formatter.tok       # EngineClient: the frontend's tokenizer
+
+
+class _LogprobFormat:
+    """Engine entries ``{"id", "logprob", "top": [(id, logprob)]}`` -> the OpenAI response objects.  ``token`` is
+    the tokenizer's decode of the single id, ``bytes`` its UTF-8 bytes; a log-probability that is not finite
+    (a masked logit) is reported as -9999.0, the API's value for "very unlikely"."""
+
+    def __init__(self, engine):
+        self.tok = _tokenizer(engine)
+        self.offset = 0                  # completions text_offset: running length of the tokens' texts
+
+    def text(self, i: int) -> str:
+        return self.tok.decode([i], skip_special_tokens=False)
+
+    @staticmethod
+    def val(x: float) -> float:
+        return x if x == x and abs(x) != float("inf") else -9999.0
+
+    def chat(self, entries) -> dict:
+        def item(i, lp):
+            t = self.text(i)
+            return {"token": t, "logprob": self.val(lp), "bytes": list(t.encode("utf-8"))}
+        return {"content": [{**item(e["id"], e["logprob"]), "top_logprobs": [item(i, lp) for i, lp in e["top"]]}
+                            for e in entries]}
+
+    def completion(self, entries) -> dict:
+        out = {"tokens": [], "token_logprobs": [], "top_logprobs": [], "text_offset": []}
+        for e in entries:
+            t = self.text(e["id"])
+            out["tokens"].append(t)
+            out["token_logprobs"].append(self.val(e["logprob"]))
+            top: dict = {}
+            for i, lp in e["top"]:       # ids whose texts coincide (partial UTF-8 bytes): the likeliest keeps the key
+                top.setdefault(self.text(i), self.val(lp))
+            out["top_logprobs"].append(top)
+            out["text_offset"].append(self.offset)
+            self.offset += len(t)
+        return out
+
+
+def create_app(engine: ServingEngine, api_key: str | None = None, moderation=None, max_logprobs: int = 20) -> FastAPI:
     """``moderation``: optional callable ``text -> dict`` (OpenAI moderation response), e.g.
-    :meth:`llm_in_practise_amd.infer.guard.GuardClient.moderate_sync`."""
+    :meth:`llm_in_practise_amd.infer.guard.GuardClient.moderate_sync`.  ``max_logprobs``: vLLM's
+    ``--max-logprobs`` — a request asking for more log-probabilities per token gets HTTP 400."""
     app = FastAPI(title="llm_in_practise_amd OpenAI-compatible server")
 
     @app.middleware("http")
@@ -156,15 +211,21 @@ def create_app(engine: ServingEngine, api_key: str | None = None, moderation=Non
         cid, created = "chatcmpl-" + uuid.uuid4().hex, int(time.time())
         name = req.model or engine.model_name
         tgt = _target(req.model)
+        params = _params(req, max_logprobs)
         if req.stream:
-            return StreamingResponse(_sse_chat(engine, prompt, _params(req), cid, created, name, tgt),
+            return StreamingResponse(_sse_chat(engine, prompt, params, cid, created, name, tgt),
                                      media_type="text/event-stream")
-        res = await asyncio.to_thread(_complete, engine, prompt, _params(req), tgt)
-        return ChatCompletionResponse(
+        res = await asyncio.to_thread(_complete, engine, prompt, params, tgt)
+        resp = ChatCompletionResponse(
             id=cid, created=created, model=name,
             choices=[Choice(index=0, message=ChoiceMessage(content=res["text"]), finish_reason=res["finish_reason"])],
             usage=Usage(prompt_tokens=res["prompt_tokens"], completion_tokens=res["completion_tokens"],
                         total_tokens=res["prompt_tokens"] + res["completion_tokens"]))
+        if params.logprobs is None:
+            return resp
+        body = resp.model_dump()
+        body["choices"][0]["logprobs"] = _LogprobFormat(engine).chat(res["logprobs"])
+        return JSONResponse(body)
 
     @app.post("/v1/completions")
     async def completions(req: CompletionRequest):
@@ -172,13 +233,15 @@ def create_app(engine: ServingEngine, api_key: str | None = None, moderation=Non
         cid, created = "cmpl-" + uuid.uuid4().hex, int(time.time())
         name = req.model or engine.model_name
         tgt = _target(req.model)
+        params = _params(req, max_logprobs)
         if req.stream:
-            return StreamingResponse(_sse_completion(engine, req.prompt, _params(req), cid, created, name, tgt),
+            return StreamingResponse(_sse_completion(engine, req.prompt, params, cid, created, name, tgt),
                                      media_type="text/event-stream")
-        res = await asyncio.to_thread(_complete, engine, req.prompt, _params(req), tgt)
+        res = await asyncio.to_thread(_complete, engine, req.prompt, params, tgt)
+        lps = None if params.logprobs is None else _LogprobFormat(engine).completion(res["logprobs"])
         return {"id": cid, "object": "text_completion", "created": created, "model": name,
                 "choices": [{"index": 0, "text": res["text"], "finish_reason": res["finish_reason"],
-                             "logprobs": None}],
+                             "logprobs": lps}],
                 "usage": {"prompt_tokens": res["prompt_tokens"], "completion_tokens": res["completion_tokens"],
                           "total_tokens": res["prompt_tokens"] + res["completion_tokens"]}}
 
@@ -217,10 +280,13 @@ async def _sse_chat(engine, prompt, params, cid, created, name, model=None):
     head = {"id": cid, "object": "chat.completion.chunk", "created": created, "model": name}
     yield "data: " + json.dumps({**head, "choices": [{"index": 0, "delta": {"role": "assistant"},
                                                       "finish_reason": None}]}) + "\n\n"
+    fmt = _LogprobFormat(engine) if params.logprobs is not None else None
     async for delta, final in _aiter_stream(engine, prompt, params, model):
         if final is None:
-            yield "data: " + json.dumps({**head, "choices": [{"index": 0, "delta": {"content": delta},
-                                                              "finish_reason": None}]}, ensure_ascii=False) + "\n\n"
+            choice = {"index": 0, "delta": {"content": delta}, "finish_reason": None}
+            if fmt is not None:          # the entries of the tokens whose text this chunk carries
+                choice["logprobs"] = fmt.chat(getattr(delta, "logprobs", None) or [])
+            yield "data: " + json.dumps({**head, "choices": [choice]}, ensure_ascii=False) + "\n\n"
         else:
             yield "data: " + json.dumps({**head, "choices": [{"index": 0, "delta": {},
                                                               "finish_reason": final["finish_reason"]}]}) + "\n\n"
@@ -229,10 +295,13 @@ async def _sse_chat(engine, prompt, params, cid, created, name, model=None):
 
 async def _sse_completion(engine, prompt, params, cid, created, name, model=None):
     head = {"id": cid, "object": "text_completion", "created": created, "model": name}
+    fmt = _LogprobFormat(engine) if params.logprobs is not None else None
     async for delta, final in _aiter_stream(engine, prompt, params, model):
         fr = None if final is None else final["finish_reason"]
-        yield "data: " + json.dumps({**head, "choices": [{"index": 0, "text": delta, "finish_reason": fr}]},
-                                    ensure_ascii=False) + "\n\n"
+        choice = {"index": 0, "text": delta, "finish_reason": fr}
+        if fmt is not None:
+            choice["logprobs"] = fmt.completion(getattr(delta, "logprobs", None) or [])
+        yield "data: " + json.dumps({**head, "choices": [choice]}, ensure_ascii=False) + "\n\n"
     yield "data: [DONE]\n\n"
 
 

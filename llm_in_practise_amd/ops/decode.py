@@ -106,5 +106,37 @@ def sample(logits, history=None, temperature=1.0, top_k=0, top_p=1.0, penalty=1.
     return sample_reference(logits, history, temperature, top_k, top_p, penalty, generator)
 
 
+MAX_LOGPROBS = 20      # the sampler kernel's limit on num_top (the OpenAI API's, too)
+
+
+def sample_logprobs_reference(logits, history=None, temperature=1.0, top_k=0, top_p=1.0, penalty=1.0, num_top=0,
+                              generator=None):
+    """``sample_reference`` plus RAW log-probabilities (vLLM's default): ``lp_i = x_i − logsumexp(x)`` over the
+    row as given, in fp32 — penalty, temperature, top-k and top-p choose the token but do not enter.  Returns
+    ``(tokens [B], lp [B], top_id [B, num_top], top_lp [B, num_top])``; the top entries are ordered by value
+    descending and, among equal values, lowest token id first."""
+    if not 0 <= num_top <= min(MAX_LOGPROBS, logits.shape[-1]):
+        raise ValueError(f"num_top {num_top} outside [0, min({MAX_LOGPROBS}, V = {logits.shape[-1]})]")
+    tokens = sample_reference(logits, history, temperature, top_k, top_p, penalty, generator)
+    x = logits.float()
+    lps = torch.log_softmax(x, -1)
+    top_id = torch.sort(x, dim=-1, descending=True, stable=True).indices[:, :num_top]
+    return tokens, lps.gather(1, tokens[:, None]).squeeze(1), top_id, lps.gather(1, top_id)
+
+
+def sample_logprobs(logits, history=None, temperature=1.0, top_k=0, top_p=1.0, penalty=1.0, num_top=0, key=None,
+                    generator=None):
+    """:func:`sample` that also reports the chosen token's raw log-probability and the ``num_top`` most likely
+    tokens (see :func:`sample_logprobs_reference`).  With the same ``key`` the tokens equal :func:`sample`'s."""
+    if use_native(logits) and logits.dtype in (torch.float32, torch.bfloat16):
+        if key is None:
+            _KEY[0] = (_KEY[0] * 6364136223846793005 + 1442695040888963407) & 0x7FFFFFFFFFFFFFFF
+            key = _KEY[0]
+        h = history.to(torch.int32).contiguous() if history is not None else None
+        return tuple(native().sample_logprobs(logits.contiguous(), h, float(temperature or 0.0), int(top_k or 0),
+                                              float(top_p), float(penalty), int(num_top), int(key)))
+    return sample_logprobs_reference(logits, history, temperature, top_k, top_p, penalty, num_top, generator)
+
+
 def seed_sampler(seed: int):
     _KEY[0] = (int(seed) * 0x9E3779B97F4A7C15 + 1) & 0x7FFFFFFFFFFFFFFF

@@ -297,6 +297,15 @@ def ce_fwd_bwd64(logits, labels, ignore_index: int, row_scale):
     return loss, (p - one) * sc, (p + one) * sc.abs()
 
 
+def logprobs64(logits):
+    """-> lp [B, V] = x − logsumexp(x) of the raw rows, S [B, 1] = max|x| + ln V (the intermediates are
+    x − max and the log of a sum of V terms).  −inf logits give −inf; S counts finite entries only."""
+    x = _d(logits)
+    lp = x - torch.logsumexp(x, -1, keepdim=True)
+    fin = torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x))
+    return lp, fin.amax(-1, keepdim=True) + math.log(x.shape[-1])
+
+
 def adamw_step64(p, g, m, v, step: int, lr, b1, b2, eps, wd):
     """One AdamW step in fp64 (out of place) -> p, S(p), m, S(m), v.  p is the difference of the decayed weight
     and the update, m the sum of two terms of either sign: S is the sum of their magnitudes."""

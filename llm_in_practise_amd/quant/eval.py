@@ -35,6 +35,35 @@ def self_ppl(model, prompts: Iterable[torch.Tensor], max_new_tokens: int = 256, 
     return math.exp(-lp_sum / max(1, n))
 
 
+def self_ppl_engine(engine, prompts, max_new_tokens: int = 256) -> tuple[float, float]:
+    """The reference's figure through the serving engine, to the letter (``eval_qwen3_4b_awq.py:24-66``:
+    vLLM with ``SamplingParams(temperature=0.0, max_tokens=256, logprobs=1)``): per prompt, skip the first
+    generated token's entry, take the highest log-probability of each remaining step, ``exp(−mean)``; then
+    mean and (population) standard deviation over the prompts.  All prompts are submitted at once, so they
+    decode as a batch on the engine's own path (int4 GEMV / w4mm, hipGraph replay, KV cache).  ``prompts``:
+    strings or token-id sequences.  A prompt that generated fewer than 2 tokens has no figure and is left
+    out, as the reference leaves it out.  -> (mean, std)."""
+    from ..infer.engine import SamplingParams
+    p = SamplingParams(max_tokens=max_new_tokens, temperature=0.0, logprobs=1)
+    reqs = [engine.submit(q.tolist() if isinstance(q, torch.Tensor) else q, p) for q in prompts]
+    ppls = []
+    for r in reqs:
+        out = getattr(r, "out", r)               # EngineClient.submit returns the queue itself
+        while True:
+            kind, val = out.get()
+            if kind == "error":
+                raise RuntimeError(val)
+            if kind == "final":
+                break
+        best = [max(lp for _, lp in e["top"]) for e in val["logprobs"][1:]]
+        if best:
+            ppls.append(math.exp(-sum(best) / len(best)))
+    if not ppls:
+        return float("nan"), float("nan")
+    mean = sum(ppls) / len(ppls)
+    return mean, math.sqrt(sum((x - mean) ** 2 for x in ppls) / len(ppls))
+
+
 @torch.no_grad()
 def dataset_ppl(model, ids: torch.Tensor, block: int = 512) -> float:
     ids = ids.view(-1)

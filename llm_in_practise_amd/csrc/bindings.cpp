@@ -1,6 +1,7 @@
 // PyTorch bindings for the gfx950 kernels.  Launchers take raw pointers + the current HIP
 // stream (so every op is capturable in a hipGraph and ordered with PyTorch's own work).
 #include "kernels/lora_epi.h"
+#include "kernels/sample_rows.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
@@ -133,6 +134,8 @@ void launch_sample(int, const void*, const int*, int, float*, int64_t*, int, int
                    hipStream_t);
 void launch_sample_logprobs(int, const void*, const int*, int, float*, int64_t*, float*, int64_t*, float*, int, int, int,
                             float, int, float, float, uint64_t, hipStream_t);
+void launch_sample_rows(int, const void*, float*, int*, int64_t*, int, int, const lipa::SampleRows&, float*, int64_t*,
+                        float*, int, hipStream_t);
 void* car_alloc(size_t, bool);
 void car_free(void*);
 bool car_ipc_handle(void*, char*);
@@ -1755,6 +1758,111 @@ std::vector<Tensor> sample_logprobs(Tensor logits, optional<Tensor> hist, double
   return {out, lp, top_id, top_lp};
 }
 
+// The per-row sampler (decode.hip sample_rows_k): every parameter is a [B] tensor on the logits' device, so a
+// batch of requests with different settings is one launch.  key [B] int64: >= 0 the row's own RNG key, < 0
+// derive it from call_key and the row index.  bias_id / bias_val [B, NB <= 300] (id -1 = unused) or None.
+// hist [R, Lmax] int32 with slot / prompt_len / seq_len [B] int32 (all four or none): the row reads the first
+// seq_len ints of history row slot, of which the first prompt_len are prompt.  Ids outside [0, V) and a slot
+// outside [0, R) are ignored on the device, the lengths clamped.  num_top < 0: returns {tokens}; otherwise
+// {tokens, lp, top_id, top_lp} as sample_logprobs.
+std::vector<Tensor> sample_rows(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor min_p,
+                                Tensor rep, Tensor pres, Tensor freq, Tensor key, optional<Tensor> bias_id,
+                                optional<Tensor> bias_val, optional<Tensor> hist, optional<Tensor> slot,
+                                optional<Tensor> prompt_len, optional<Tensor> seq_len, int64_t call_key,
+                                int64_t num_top) {
+  CHECK_CUDA(logits);
+  CHECK_CONTIG(logits);
+  dtype_code(logits);
+  TORCH_CHECK(logits.dim() == 2, "sample_rows: logits [B, V]");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V > 0 && V <= INT_MAX && B <= INT_MAX, "sample_rows: logits shape");
+  TORCH_CHECK(num_top < 0 || (num_top <= 20 && num_top <= V), "sample_rows: num_top ", num_top,
+              " outside [0, min(20, V = ", V, ")]");
+  auto per_row = [&](const Tensor& t, at::ScalarType ty, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device() && t.scalar_type() == ty && t.dim() == 1 &&
+                    t.size(0) == B && t.is_contiguous(),
+                "sample_rows: ", name, " must be a contiguous [B] ", ty, " tensor on the logits' device");
+  };
+  per_row(temperature, at::kFloat, "temperature");
+  per_row(top_k, at::kInt, "top_k");
+  per_row(top_p, at::kFloat, "top_p");
+  per_row(min_p, at::kFloat, "min_p");
+  per_row(rep, at::kFloat, "repetition_penalty");
+  per_row(pres, at::kFloat, "presence_penalty");
+  per_row(freq, at::kFloat, "frequency_penalty");
+  per_row(key, at::kLong, "key");
+  lipa::SampleRows a{};
+  a.temperature = temperature.data_ptr<float>();
+  a.top_k = top_k.data_ptr<int>();
+  a.top_p = top_p.data_ptr<float>();
+  a.min_p = min_p.data_ptr<float>();
+  a.rep = rep.data_ptr<float>();
+  a.pres = pres.data_ptr<float>();
+  a.freq = freq.data_ptr<float>();
+  a.key = key.data_ptr<int64_t>();
+  a.call_key = (uint64_t)call_key;
+  const bool has_bias = bias_id.has_value() && bias_id->defined();
+  TORCH_CHECK(has_bias == (bias_val.has_value() && bias_val->defined()), "sample_rows: bias_id and bias_val go together");
+  if (has_bias) {
+    TORCH_CHECK(bias_id->is_cuda() && bias_id->get_device() == logits.get_device() &&
+                    bias_id->scalar_type() == at::kInt && bias_id->dim() == 2 && bias_id->size(0) == B &&
+                    bias_id->is_contiguous(),
+                "sample_rows: bias_id must be a contiguous [B, NB] int32 tensor on the logits' device");
+    TORCH_CHECK(bias_val->is_cuda() && bias_val->get_device() == logits.get_device() &&
+                    bias_val->scalar_type() == at::kFloat && bias_val->is_contiguous() &&
+                    bias_val->sizes() == bias_id->sizes(),
+                "sample_rows: bias_val must be a contiguous float32 tensor of bias_id's shape");
+    TORCH_CHECK(bias_id->size(1) <= lipa::SAMPLE_ROWS_MAX_BIAS, "sample_rows: NB ", bias_id->size(1), " > ",
+                lipa::SAMPLE_ROWS_MAX_BIAS);
+    a.NB = (int)bias_id->size(1);
+    if (a.NB > 0) {
+      a.bias_id = bias_id->data_ptr<int>();
+      a.bias_val = bias_val->data_ptr<float>();
+    }
+  }
+  const bool has_hist = hist.has_value() && hist->defined();
+  auto given = [](const optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  TORCH_CHECK(has_hist == given(slot) && has_hist == given(prompt_len) && has_hist == given(seq_len),
+              "sample_rows: hist, slot, prompt_len and seq_len go together");
+  Tensor cnt;
+  if (has_hist) {
+    TORCH_CHECK(hist->is_cuda() && hist->get_device() == logits.get_device() && hist->scalar_type() == at::kInt &&
+                    hist->dim() == 2 && hist->is_contiguous(),
+                "sample_rows: hist must be a contiguous [R, Lmax] int32 tensor on the logits' device");
+    TORCH_CHECK(hist->size(0) <= INT_MAX && hist->size(1) < (1 << 30), "sample_rows: hist shape");
+    per_row(*slot, at::kInt, "slot");
+    per_row(*prompt_len, at::kInt, "prompt_len");
+    per_row(*seq_len, at::kInt, "seq_len");
+    a.R = (int)hist->size(0);       // a slot outside [0, R) reads no history (checked per row on the device)
+    a.Lmax = (int)hist->size(1);
+    if (a.R > 0 && a.Lmax > 0) {
+      a.hist = hist->data_ptr<int>();
+      a.slot = slot->data_ptr<int>();
+      a.prompt_len = prompt_len->data_ptr<int>();
+      a.seq_len = seq_len->data_ptr<int>();
+      cnt = at::empty({B, V}, logits.options().dtype(at::kInt));
+    }
+  }
+  Tensor work = at::empty({B, V}, logits.options().dtype(at::kFloat));
+  Tensor out = at::empty({B}, logits.options().dtype(at::kLong));
+  if (num_top < 0) {
+    if (B > 0)
+      launch_sample_rows(dtype_code(logits), logits.data_ptr(), work.data_ptr<float>(),
+                         cnt.defined() ? cnt.data_ptr<int>() : nullptr, out.data_ptr<int64_t>(), B, V, a, nullptr,
+                         nullptr, nullptr, 0, stream());
+    return {out};
+  }
+  Tensor lp = at::empty({B}, logits.options().dtype(at::kFloat));
+  Tensor top_id = at::empty({B, num_top}, logits.options().dtype(at::kLong));
+  Tensor top_lp = at::empty({B, num_top}, logits.options().dtype(at::kFloat));
+  if (B > 0)
+    launch_sample_rows(dtype_code(logits), logits.data_ptr(), work.data_ptr<float>(),
+                       cnt.defined() ? cnt.data_ptr<int>() : nullptr, out.data_ptr<int64_t>(), B, V, a,
+                       lp.data_ptr<float>(), top_id.data_ptr<int64_t>(), top_lp.data_ptr<float>(), (int)num_top,
+                       stream());
+  return {out, lp, top_id, top_lp};
+}
+
 }  // namespace
 
 
@@ -1923,6 +2031,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_w4", &gemv_w4);
   m.def("sample", &sample);
   m.def("sample_logprobs", &sample_logprobs);
+  m.def("sample_rows", &sample_rows);
   m.def("adamw", &adamw);
   m.def("adamw8bit", &adamw8bit);
   m.def("host_mapped_empty", &host_mapped_empty, py::arg("numel"), py::arg("dtype"));

@@ -21,7 +21,9 @@
 // The log-probability variant (sample_k<T, true>) picks the token in exactly the same way and adds
 // an epilogue over the RAW row: lp_i = x_i - logsumexp(x) of the chosen token and of the N most
 // likely tokens, ordered by (value descending, id ascending).
+// sample_rows_k is the same sampler with every parameter per row (serving: mixed batches in one launch).
 #include "common.h"
+#include "sample_rows.h"
 
 #include <algorithm>
 
@@ -591,6 +593,194 @@ __global__ __launch_bounds__(SMP_THR) void sample_k(const T* __restrict__ logits
   }
 }
 
+// Per-row sampler (ops/decode.py sample_rows_reference has the semantics): every sampling parameter is a
+// [B] array, so one launch serves a batch of requests with different settings.  Same scheme as sample_k (one
+// 1024-thread workgroup per row, fp32 work row, threshold bisection, block scan), plus logit bias, the
+// OpenAI presence / frequency penalties, min_p and a per-row RNG key.
+//
+// Duplicate history tokens: a per-row int32 word `cnt[V]` beside the work row, cleared in the fill pass.  One
+// pass over the live history does integer atomics on it (order-independent): bit 30 = "in the prompt",
+// bits 0..29 = occurrences in the output.  The arg-max pass then applies the repetition, frequency and
+// presence penalties to every marked entry, once, from that word.  No float is read-modified-written by more
+// than one thread.  A row whose three penalties are neutral (or whose history is empty) never touches `cnt`.
+// Bias entries: thread j applies entry j only if no earlier entry names the same token, and adds the later
+// duplicates itself, in table order.
+constexpr int SMP_MAX_BIAS = SAMPLE_ROWS_MAX_BIAS;
+constexpr int SMP_PROMPT_BIT = 1 << 30;
+
+template <typename T, bool LP = false>
+__global__ __launch_bounds__(SMP_THR) void sample_rows_k(const T* __restrict__ logits, float* __restrict__ work,
+                                                         int* __restrict__ cnt, int64_t* __restrict__ out, int V,
+                                                         SampleRows a, SampleLp lpo = SampleLp{}) {
+  __shared__ float red[SMP_NW];
+  __shared__ float sc[SMP_THR];
+  __shared__ int si[SMP_NW];
+  __shared__ int s_pick;
+  __shared__ int s_bid[SMP_MAX_BIAS];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const T* x = logits + (size_t)row * V;
+  float* wv = work + (size_t)row * V;
+  int* cw = cnt + (size_t)row * V;
+  const float temperature = a.temperature[row], top_p = a.top_p[row], min_p = a.min_p[row];
+  const float rep = a.rep[row], pres = a.pres[row], freq = a.freq[row];
+  const int top_k = a.top_k[row];
+  // the live part of this row's history: [0, pl) prompt, [pl, sl) output
+  int sl = 0, pl = 0;
+  const int* h = nullptr;
+  if (a.hist) {
+    const int s = a.slot[row];
+    if (s >= 0 && s < a.R) {
+      h = a.hist + (size_t)s * a.Lmax;
+      sl = min(max(a.seq_len[row], 0), a.Lmax);
+      pl = min(max(a.prompt_len[row], 0), sl);
+    }
+  }
+  const bool pen = sl > 0 && (rep != 1.f || pres != 0.f || freq != 0.f);   // uniform over the workgroup
+  if (pen) {
+    for (int i = tid; i < V; i += SMP_THR) { wv[i] = (float)x[i]; cw[i] = 0; }
+  } else {
+    for (int i = tid; i < V; i += SMP_THR) wv[i] = (float)x[i];
+  }
+  const int nb = min(a.NB, SMP_MAX_BIAS);
+  for (int j = tid; j < nb; j += SMP_THR) s_bid[j] = a.bias_id[(size_t)row * a.NB + j];
+  __syncthreads();
+  if (tid < nb) {    // ---- 1. logit bias
+    const int id = s_bid[tid];
+    if (id >= 0 && id < V) {
+      bool first = true;
+      for (int j = 0; j < tid; ++j) first = first && s_bid[j] != id;
+      if (first) {
+        float y = wv[id];
+        for (int j = tid; j < nb; ++j)
+          if (s_bid[j] == id) y = __fadd_rn(y, a.bias_val[(size_t)row * a.NB + j]);
+        wv[id] = y;
+      }
+    }
+  }
+  if (pen) {
+    for (int i = tid; i < sl; i += SMP_THR) {
+      const int id = h[i];
+      if (id >= 0 && id < V) {
+        // workgroup scope: the row belongs to this workgroup alone (sl <= Lmax < 2^30: the count cannot carry)
+        if (i < pl)
+          __hip_atomic_fetch_or(&cw[id], SMP_PROMPT_BIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else
+          __hip_atomic_fetch_add(&cw[id], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+  }
+  __syncthreads();
+  // ---- 2., 3. penalties, fused with max + argmax (lowest index wins ties)
+  float best = -INFINITY;
+  int bidx = 0x7FFFFFFF;
+  for (int i = tid; i < V; i += SMP_THR) {
+    float v = wv[i];
+    if (pen) {
+      const int c = __hip_atomic_load(&cw[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (c) {
+        if (rep != 1.f) v = v < 0.f ? __fmul_rn(v, rep) : __fdiv_rn(v, rep);
+        const int n = c & (SMP_PROMPT_BIT - 1);
+        if (n) v = __fsub_rn(__fsub_rn(v, __fmul_rn(freq, (float)n)), pres);
+        wv[i] = v;
+      }
+    }
+    if (v > best || (v == best && i < bidx)) { best = v; bidx = i; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bidx, o, 64);
+    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+  }
+  if ((tid & 63) == 0) { red[tid >> 6] = best; si[tid >> 6] = bidx; }
+  __syncthreads();
+  best = red[0];
+  bidx = si[0];
+  for (int i = 1; i < SMP_NW; ++i)
+    if (red[i] > best || (red[i] == best && si[i] < bidx)) { best = red[i]; bidx = si[i]; }
+  __syncthreads();
+  if (!(temperature > 0.f)) {  // ---- 4. greedy
+    if constexpr (LP) {
+      sample_logprobs_epilogue(x, V, row, bidx, lpo, out, red);
+    } else {
+      if (tid == 0) out[row] = bidx;
+    }
+    return;
+  }
+  // the argmax stands unless the draw below picks (no kept mass); ordered before the pick by the scan's barriers
+  if (tid == 0) {
+    if constexpr (LP) s_pick = bidx; else out[row] = bidx;
+  }
+  // ---- 5. temperature; thresholds on the unnormalised p_i = exp(y_i/T - max), whose maximum is exactly 1
+  const float invT = 1.f / temperature;
+  const float mx = best * invT;
+  auto prob = [&](int i) { return __expf(wv[i] * invT - mx); };
+  float lo = 0.f, hi = 1.f;
+  // min_p: p_i >= min_p * max p.  Top-k over what is left is the top-k threshold over the whole row, raised
+  // to min_p (fewer than k left: all of them stay).
+  float thr = 0.f;
+  if (top_k > 0 && top_k < V) {
+    for (int it = 0; it < 40; ++it) {
+      const float mid = 0.5f * (lo + hi);
+      float c = 0.f;
+      for (int i = tid; i < V; i += SMP_THR) c += prob(i) >= mid ? 1.f : 0.f;
+      c = bsum(c, red);
+      if (c >= (float)top_k) lo = mid; else hi = mid;
+    }
+    thr = lo;
+  }
+  if (min_p > 0.f) thr = fmaxf(thr, fminf(min_p, 1.f));
+  // top-p over the kept set: largest t >= thr with mass(p >= t) >= top_p * mass(kept)
+  if (top_p < 1.f) {
+    float tot = 0.f;
+    for (int i = tid; i < V; i += SMP_THR) { const float p = prob(i); tot += p >= thr ? p : 0.f; }
+    tot = bsum(tot, red);
+    lo = thr; hi = 1.f;
+    for (int it = 0; it < 40; ++it) {
+      const float mid = 0.5f * (lo + hi);
+      float c = 0.f;
+      for (int i = tid; i < V; i += SMP_THR) { const float p = prob(i); c += p >= mid ? p : 0.f; }
+      c = bsum(c, red);
+      if (c >= top_p * tot) lo = mid; else hi = mid;
+    }
+    thr = lo;
+  }
+  // inverse-CDF draw over kept tokens in index order: contiguous chunk per thread
+  const int per = (V + SMP_THR - 1) / SMP_THR;
+  const int i0 = min(tid * per, V), i1 = min(i0 + per, V);
+  float mine = 0.f;
+  for (int i = i0; i < i1; ++i) { const float p = prob(i); mine += p >= thr ? p : 0.f; }
+  sc[tid] = mine;
+  __syncthreads();
+  for (int off = 1; off < SMP_THR; off <<= 1) {  // inclusive Hillis-Steele scan
+    const float add = tid >= off ? sc[tid - off] : 0.f;
+    __syncthreads();
+    sc[tid] += add;
+    __syncthreads();
+  }
+  const float total = sc[SMP_THR - 1];
+  // ---- 6. the row's own key, or (call key, row index) as sample_k
+  const int64_t rk = a.key[row];
+  const uint64_t r = rk >= 0 ? mix64((uint64_t)rk) : mix64(a.call_key ^ mix64((uint64_t)row + 0x1234567ull));
+  const float u = (float)((r >> 40) * (1.0 / 16777216.0)) * total;
+  const float before = tid ? sc[tid - 1] : 0.f;
+  if (u >= before && u < sc[tid] && mine > 0.f) {
+    float run = before;
+    int pick = i1 - 1;
+    for (int i = i0; i < i1; ++i) {
+      const float p = prob(i);
+      if (p < thr) continue;
+      run += p;
+      if (u < run) { pick = i; break; }
+    }
+    if constexpr (LP) s_pick = pick; else out[row] = pick;
+  }
+  if constexpr (LP) {
+    __syncthreads();             // the pick was written by one thread: make it visible
+    sample_logprobs_epilogue(x, V, row, s_pick, lpo, out, red);
+  }
+}
+
 }  // namespace
 
 // Split-K plan: enough (split, kv-head, sequence) workgroups to fill the chip.  The number of
@@ -675,5 +865,25 @@ void launch_sample_logprobs(int dtype, const void* logits, const int* hist, int 
   else
     sample_k<bf16, true><<<B, SMP_THR, 0, st>>>((const bf16*)logits, hist, hist_len, work, out, V, temperature,
                                                 top_k, top_p, penalty, key, o);
+  LIPA_CHECK_LAUNCH();
+}
+
+// One launch for a batch with per-row sampling parameters (sample_rows_k).  cnt [B, V] int32 may be null when
+// hist is.  With lp != null the log-probability variant runs: lp [B], top_id / top_lp [B, num_top].
+void launch_sample_rows(int dtype, const void* logits, float* work, int* cnt, int64_t* out, int B, int V,
+                        const lipa::SampleRows& a, float* lp, int64_t* top_id, float* top_lp, int num_top,
+                        hipStream_t st) {
+  if (lp) {
+    const SampleLp o{lp, top_id, top_lp, num_top};
+    if (dtype == 0)
+      sample_rows_k<float, true><<<B, SMP_THR, 0, st>>>((const float*)logits, work, cnt, out, V, a, o);
+    else
+      sample_rows_k<bf16, true><<<B, SMP_THR, 0, st>>>((const bf16*)logits, work, cnt, out, V, a, o);
+  } else {
+    if (dtype == 0)
+      sample_rows_k<float><<<B, SMP_THR, 0, st>>>((const float*)logits, work, cnt, out, V, a);
+    else
+      sample_rows_k<bf16><<<B, SMP_THR, 0, st>>>((const bf16*)logits, work, cnt, out, V, a);
+  }
   LIPA_CHECK_LAUNCH();
 }

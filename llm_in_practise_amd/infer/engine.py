@@ -15,8 +15,9 @@ per slot affordable: Qwen3-8B, 64 slots × 4096 tokens = 36 GB):
   whole batch);
 * finished rows (EOS / max_tokens / cache full) are released immediately and refilled on the next
   iteration — no request waits for another's completion;
-* per-request sampling parameters: rows are sampled in groups of identical parameters with the
-  fused sampler kernel.
+* per-request sampling parameters: a step whose rows share one parameter set runs the fused sampler
+  kernel; any other step (mixed parameters, presence / frequency penalty, min_p, logit_bias, seed) is
+  one launch of the per-row sampler, which reads a device-resident token history.
 
 Streaming requests receive text deltas per token; ``/metrics`` data (Prometheus text) is kept here.
 """
@@ -32,7 +33,7 @@ from typing import Any
 import torch
 
 from ..models.common import KVCache, PackedPrefill
-from ..ops.decode import MAX_LOGPROBS, sample, sample_logprobs
+from ..ops.decode import MAX_LOGIT_BIAS, MAX_LOGPROBS, sample, sample_logprobs, sample_rows, seed_key
 from ..ops.linear import head_logits
 from ..train.data import render_chatml
 
@@ -49,9 +50,23 @@ class SamplingParams:
     # vLLM ``SamplingParams.logprobs``: None = off, 0 = the sampled token's raw log-probability only,
     # k in 1..20 = plus the k most likely tokens of the raw distribution (ops.decode.sample_logprobs)
     logprobs: int | None = None
+    # OpenAI / vLLM request parameters served by the per-row sampler (ops.decode.sample_rows_reference)
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    min_p: float = 0.0
+    logit_bias: dict[int, float] | None = None      # token id -> added to the logit (at most MAX_LOGIT_BIAS)
+    seed: int | None = None                         # the request's own random stream
 
     def key(self):
         return (self.temperature, self.top_p, self.top_k, self.repetition_penalty)
+
+    def per_row(self) -> bool:
+        """Does the request use a parameter only the per-row sampler serves?"""
+        return bool(self.presence_penalty or self.frequency_penalty or self.min_p > 0 or self.logit_bias
+                    or self.seed is not None)
+
+    def needs_history(self) -> bool:
+        return self.repetition_penalty != 1.0 or bool(self.presence_penalty or self.frequency_penalty)
 
 
 class Delta(str):
@@ -303,6 +318,7 @@ class _Slot:
     lps: list | None = None              # one entry per sampled token (a terminating EOS included), if asked for
     lp_sent: int = 0                     # entries already streamed
     eos_tok: int | None = None           # the EOS token the request ended on (not part of gen)
+    nsamp: int = 0                       # tokens sampled for this request so far (the counter of a seeded stream)
 
     def __post_init__(self):
         if self.req.params.logprobs is not None:
@@ -461,6 +477,9 @@ class ServingEngine:
                 self._adapter_salt[i] = f"{n}={(lora_modules or {}).get(n, '')}".encode()
         self.slots: list[_Slot | None] = [None] * max_batch
         self.next_tok = torch.full((max_batch,), self.pad, dtype=torch.long, device=self.device)
+        # device-resident token history of the slots whose request has a penalty: allocated on the first one
+        self.hist = self.hist_plen = self.hist_len = None
+        self._rows_cache = None                  # (batch composition, device parameter tensors) of sample_rows
         self.graphs = None
         if use_graphs is None:
             use_graphs = self.device.type == "cuda"
@@ -522,6 +541,10 @@ class ServingEngine:
         """``/v1/models``: the base model plus every LoRA adapter name."""
         return [self.model_name] + (list(self.mlora.names) if self.mlora is not None else [])
 
+    @property
+    def vocab_size(self) -> int:
+        return int(self.lm.lm_head.weight.shape[0])
+
     def adapter_id(self, model: str | None) -> int:
         """Request ``model`` → adapter index; KeyError for a model this server does not serve."""
         if model is None or model == self.model_name:
@@ -538,6 +561,12 @@ class ServingEngine:
         k = params.logprobs
         if k is not None and not 0 <= k <= min(MAX_LOGPROBS, self.lm.lm_head.weight.shape[0]):
             raise ValueError(f"logprobs {k}: must be None or in 0..{MAX_LOGPROBS}")
+        if params.logit_bias:
+            bias = {int(t): float(v) for t, v in params.logit_bias.items()}
+            if len(bias) > MAX_LOGIT_BIAS or not all(0 <= t < self.vocab_size for t in bias):
+                raise ValueError(f"logit_bias: at most {MAX_LOGIT_BIAS} entries with token ids in "
+                                 f"[0, {self.vocab_size})")
+            params = dataclasses.replace(params, logit_bias=bias)
         room = self.max_len - 1 - min(params.max_tokens, self.max_len // 2)   # keep space to generate
         # (a prompt given as token ids is taken as it is: quant/eval.py self_ppl_engine)
         ids = (self.encode(prompt) if isinstance(prompt, str) else [int(t) for t in prompt])[-room:]
@@ -751,6 +780,7 @@ class ServingEngine:
         s.prefilled = -1
         self.stats["prompt_tokens_total"] += L
         logits = head_logits(h[-1:], self.lm.lm_head.weight)
+        self._hist_admit(slot, r)
         dev_toks, toks, ents = self._sample(logits, [slot])
         self.next_tok[slot] = dev_toks[0]
         if self.prefix is not None:
@@ -773,6 +803,7 @@ class ServingEngine:
         self.cache.pos[slot] = L
         self.slots[slot] = _Slot(r)
         self.stats["prompt_tokens_total"] += L
+        self._hist_admit(slot, r)
         dev_toks, toks, ents = self._sample(logits, [slot])
         self.next_tok[slot] = dev_toks[0]
         self._accept(slot, toks[0], time.time(), ents[0])
@@ -797,11 +828,41 @@ class ServingEngine:
         for b, (slot, r) in enumerate(new):
             self.slots[slot] = _Slot(r)
             self.stats["prompt_tokens_total"] += len(r.prompt_ids)
+            self._hist_admit(slot, r)
         dev_toks, toks, ents = self._sample(logits, [s for s, _ in new])
         self.next_tok[rows] = dev_toks
         for b, (slot, r) in enumerate(new):
             self._accept(slot, toks[b], now, ents[b])
         self.stats["batches_total"] += 1
+
+    def _hist_admit(self, slot: int, r: _Request):
+        """A request with a repetition, presence or frequency penalty: its prompt goes into the slot's row of
+        the device-resident token history, once.  Every later token is appended on the device (:meth:`_hist_append`),
+        so no decode step rebuilds or uploads a history.  The buffer is allocated by the first such request."""
+        if not r.params.needs_history():
+            return
+        if self.hist is None:
+            self.hist = torch.full((self.max_batch, self.max_len), -1, dtype=torch.int32, device=self.device)
+            self.hist_plen = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+            self.hist_len = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+        L = min(len(r.prompt_ids), self.max_len)
+        self.hist[slot, :L] = torch.tensor(r.prompt_ids[:L], dtype=torch.int32).to(self.device)
+        self.hist_plen[slot] = L
+        self.hist_len[slot] = L
+
+    def _hist_append(self, slot_ids, toks):
+        """Append the step's sampled tokens (a device tensor, one per row of ``slot_ids``) to the history rows
+        of the slots that keep one — on the device, without a host sync."""
+        if self.hist is None:
+            return
+        js = [j for j, s in enumerate(slot_ids) if self.slots[s].req.params.needs_history()]
+        if not js:
+            return
+        rows = torch.tensor([slot_ids[j] for j in js], dtype=torch.long).to(self.device)
+        new = toks if len(js) == len(slot_ids) else toks[torch.tensor(js, dtype=torch.long).to(self.device)]
+        n = self.hist_len[rows]
+        self.hist[rows, n.clamp(max=self.max_len - 1).long()] = new.to(torch.int32)
+        self.hist_len[rows] = (n + 1).clamp(max=self.max_len)
 
     def _sample(self, logits, slot_ids):
         """Sample one token per row, grouping rows with identical sampling parameters.
@@ -839,6 +900,53 @@ class ServingEngine:
         """-> (tokens, None), or (tokens, (lp [n], top_id [n, N], top_lp [n, N])) when a row asks for
         log-probabilities (N = the largest request; a group of rows in which nobody asks runs plain
         ``sample``, so a step without such requests launches exactly what it always did)."""
+        params = [self.slots[s].req.params for s in slot_ids]
+        if len({p.key() for p in params}) > 1 or any(p.per_row() for p in params):
+            out, lpt = self._sample_rows_dev(logits, slot_ids, params)
+        else:
+            out, lpt = self._sample_uniform_dev(logits, slot_ids)
+        for s in slot_ids:
+            self.slots[s].nsamp += 1
+        self._hist_append(slot_ids, out)
+        return out, lpt
+
+    def _sample_rows_dev(self, logits, slot_ids, params):
+        """A step whose rows differ in their sampling parameters, or use one that only the per-row sampler
+        serves: ONE ``sample_rows`` launch over the logits as they are, the history read on the device."""
+        comp = tuple((s, self.slots[s].req.rid) for s in slot_ids)
+        if self._rows_cache is None or self._rows_cache[0] != comp:
+            dev = self.device
+            fl = torch.tensor([[float(p.temperature or 0.0) for p in params], [float(p.top_p) for p in params],
+                               [float(p.min_p) for p in params], [float(p.repetition_penalty) for p in params],
+                               [float(p.presence_penalty) for p in params],
+                               [float(p.frequency_penalty) for p in params]], dtype=torch.float32).to(dev)
+            it = torch.tensor([[int(p.top_k or 0) for p in params], list(slot_ids)], dtype=torch.int32).to(dev)
+            bias_id = bias_val = None
+            nb = max(len(p.logit_bias or ()) for p in params)
+            if nb:
+                bi = torch.full((len(params), nb), -1, dtype=torch.int32)
+                bv = torch.zeros(len(params), nb, dtype=torch.float32)
+                for j, p in enumerate(params):
+                    for q, (t, v) in enumerate((p.logit_bias or {}).items()):
+                        bi[j, q], bv[j, q] = int(t), float(v)
+                bias_id, bias_val = bi.to(dev), bv.to(dev)
+            unseeded = torch.full((len(params),), -1, dtype=torch.int64).to(dev)
+            self._rows_cache = (comp, (fl, it, it[1].long(), bias_id, bias_val, unseeded))
+        fl, it, rows, bias_id, bias_val, keys = self._rows_cache[1]
+        if any(p.seed is not None for p in params):
+            keys = torch.tensor([-1 if p.seed is None else seed_key(p.seed, self.slots[s].nsamp)
+                                 for s, p in zip(slot_ids, params)], dtype=torch.int64).to(self.device)
+        hist = plen = slen = slot = None
+        if self.hist is not None and any(p.needs_history() for p in params):
+            hist, slot, plen, slen = self.hist, it[1], self.hist_plen[rows], self.hist_len[rows]
+        want = [p.logprobs for p in params]
+        nmax = max((k for k in want if k is not None), default=None)
+        res = sample_rows(logits, fl[0], it[0], fl[1], fl[2], fl[3], fl[4], fl[5], keys, bias_id, bias_val, hist, slot,
+                          plen, slen, num_top=nmax)
+        return (res, None) if nmax is None else (res[0], tuple(res[1:]))
+
+    def _sample_uniform_dev(self, logits, slot_ids):
+        """All rows share one parameter set of the scalar sampler: ``sample`` / ``sample_logprobs``."""
         out = torch.empty(len(slot_ids), dtype=torch.long, device=self.device)
         want = [self.slots[s].req.params.logprobs for s in slot_ids]
         nmax = max((k for k in want if k is not None), default=None)
@@ -966,7 +1074,12 @@ class ServingEngine:
         rows = torch.tensor(active, device=self.device)
         if len(active) != n:
             logits = logits[rows]
-        if self.pipeline and all(self.slots[s].req.params.repetition_penalty == 1.0 for s in active):
+        ps = [self.slots[s].req.params for s in active]
+        # (the scalar sampler's repetition penalty reads the history from the host's token lists, which the
+        # asynchronous form leaves one step behind; the per-row sampler reads the device-resident history)
+        host_hist = ps[0].repetition_penalty != 1.0 and len({p.key() for p in ps}) == 1 and \
+            not any(p.per_row() for p in ps)
+        if self.pipeline and not host_hist:
             # asynchronous: the sampled tokens stay on the device (next step's input), a pinned
             # copy + event hand them to the host, and the host accepts the PREVIOUS step's
             # tokens while this step runs on the GPU (a finished request decodes one extra,

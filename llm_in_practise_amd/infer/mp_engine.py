@@ -57,7 +57,7 @@ def _engine_main(factory, factory_args, cmd_conn, out_conn, ready):
             out_conn.send(batch)
 
     eng.iteration_hook = flush
-    ready.send({"model_name": eng.model_name, "served_models": eng.served_models})
+    ready.send({"model_name": eng.model_name, "served_models": eng.served_models, "vocab_size": eng.vocab_size})
     while True:
         try:
             msg = cmd_conn.recv()
@@ -107,6 +107,7 @@ class EngineClient:
             raise RuntimeError("engine process did not start")
         info = rd_r.recv()
         self.model_name, self.served_models = info["model_name"], info["served_models"]
+        self.vocab_size = info["vocab_size"]          # the frontend validates logit_bias token ids against it
         self.formatter = formatter
         self._outs: dict[str, object] = {}
         self._send_lock = threading.Lock()

@@ -28,6 +28,7 @@ from fastapi import FastAPI, HTTPException, Request
 from fastapi.responses import JSONResponse, PlainTextResponse, StreamingResponse
 from pydantic import BaseModel, Field
 
+from ..ops.decode import MAX_LOGIT_BIAS
 from .engine import SamplingParams, ServingEngine
 
 
@@ -49,6 +50,12 @@ class ChatCompletionRequest(BaseModel):
     ignore_eos: bool = False
     logprobs: bool = False
     top_logprobs: Optional[int] = Field(None, ge=0)      # needs logprobs; capped by --max-logprobs (400 above it)
+    # served by the per-row sampler; range-checked in _params (a violation is a 400 that names the field)
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    min_p: float = 0.0
+    seed: Optional[int] = None
+    logit_bias: Optional[dict[Union[int, str], float]] = None   # token id (JSON object keys are strings) -> bias
 
 
 class CompletionRequest(BaseModel):
@@ -63,6 +70,12 @@ class CompletionRequest(BaseModel):
     stop: Optional[Union[str, list[str]]] = None
     ignore_eos: bool = False
     logprobs: Optional[int] = Field(None, ge=0)          # capped by --max-logprobs (400 above it)
+    # served by the per-row sampler; range-checked in _params (a violation is a 400 that names the field)
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    min_p: float = 0.0
+    seed: Optional[int] = None
+    logit_bias: Optional[dict[Union[int, str], float]] = None   # token id (JSON object keys are strings) -> bias
 
 
 class ChoiceMessage(BaseModel):
@@ -91,7 +104,39 @@ class ChatCompletionResponse(BaseModel):
     usage: Usage
 
 
-def _params(req, max_logprobs: int = 20) -> SamplingParams:
+def _bad(field: str, why: str):
+    raise HTTPException(status_code=400, detail=f"{field}: {why}")
+
+
+def _row_params(req, vocab_size: int | None) -> dict:
+    """The per-row sampling fields of a request, validated as the OpenAI API / vLLM do."""
+    for f in ("presence_penalty", "frequency_penalty"):
+        if not -2.0 <= getattr(req, f) <= 2.0:            # (a NaN fails every comparison: refused too)
+            _bad(f, "must be in [-2, 2]")
+    if not 0.0 <= req.min_p <= 1.0:
+        _bad("min_p", "must be in [0, 1]")
+    if req.seed is not None and not 0 <= req.seed < 2 ** 63:
+        _bad("seed", "must be an integer >= 0")
+    bias = None
+    if req.logit_bias:
+        if len(req.logit_bias) > MAX_LOGIT_BIAS:
+            _bad("logit_bias", f"at most {MAX_LOGIT_BIAS} entries")
+        bias = {}
+        for k, v in req.logit_bias.items():
+            try:
+                t = int(k)
+            except (TypeError, ValueError):
+                _bad("logit_bias", f"key {k!r} is not a token id")
+            if t < 0 or (vocab_size is not None and t >= vocab_size):
+                _bad("logit_bias", f"token id {t} outside the vocabulary")
+            if not -100.0 <= v <= 100.0:
+                _bad("logit_bias", f"value {v} for token {t} outside [-100, 100]")
+            bias[t] = float(v)
+    return dict(presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty, min_p=req.min_p,
+                seed=req.seed, logit_bias=bias)
+
+
+def _params(req, max_logprobs: int = 20, vocab_size: int | None = None) -> SamplingParams:
     stop = [req.stop] if isinstance(req.stop, str) else req.stop
     if isinstance(req, ChatCompletionRequest):
         if req.top_logprobs is not None and not req.logprobs:
@@ -103,7 +148,7 @@ def _params(req, max_logprobs: int = 20) -> SamplingParams:
         raise HTTPException(status_code=400, detail=f"{k} logprobs requested, at most {max_logprobs} are served")
     return SamplingParams(max_tokens=req.max_tokens, temperature=req.temperature, top_p=req.top_p, top_k=req.top_k,
                           repetition_penalty=req.repetition_penalty, stop=stop,
-                          ignore_eos=req.ignore_eos, logprobs=k)
+                          ignore_eos=req.ignore_eos, logprobs=k, **_row_params(req, vocab_size))
 
 
 def _tokenizer(engine):
@@ -211,7 +256,7 @@ def create_app(engine: ServingEngine, api_key: str | None = None, moderation=Non
         cid, created = "chatcmpl-" + uuid.uuid4().hex, int(time.time())
         name = req.model or engine.model_name
         tgt = _target(req.model)
-        params = _params(req, max_logprobs)
+        params = _params(req, max_logprobs, getattr(engine, "vocab_size", None))
         if req.stream:
             return StreamingResponse(_sse_chat(engine, prompt, params, cid, created, name, tgt),
                                      media_type="text/event-stream")
@@ -233,7 +278,7 @@ def create_app(engine: ServingEngine, api_key: str | None = None, moderation=Non
         cid, created = "cmpl-" + uuid.uuid4().hex, int(time.time())
         name = req.model or engine.model_name
         tgt = _target(req.model)
-        params = _params(req, max_logprobs)
+        params = _params(req, max_logprobs, getattr(engine, "vocab_size", None))
         if req.stream:
             return StreamingResponse(_sse_completion(engine, req.prompt, params, cid, created, name, tgt),
                                      media_type="text/event-stream")

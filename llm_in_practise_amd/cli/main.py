@@ -538,6 +538,28 @@ def _serving_engine_from_args(a, tp=None, tpg=None, ppg=None):
                          use_graphs=False if g("enforce_eager") else None)
 
 
+def _serve_task(a) -> str:
+    """``--task embed`` or vLLM 0.11's ``--runner pooling`` select the embedding engine; the default is generate."""
+    if getattr(a, "task", None) in ("embed", "embedding") or getattr(a, "runner", None) == "pooling":
+        return "embed"
+    return "generate"
+
+
+def cmd_embed(a):
+    """Offline: the ``/v1/embeddings`` response for ``--input`` texts, printed as JSON."""
+    from ..infer.embed import engine_from_args
+    eng = engine_from_args(a)
+    try:
+        ids = [eng.tokenize(t) for t in a.input]
+        vecs = eng.embed(ids, a.dimensions)
+    finally:
+        eng.shutdown()
+    n = sum(len(i) for i in ids)
+    print(json.dumps({"object": "list", "model": eng.model_name,
+                      "data": [{"object": "embedding", "index": i, "embedding": v} for i, v in enumerate(vecs)],
+                      "usage": {"prompt_tokens": n, "total_tokens": n}}))
+
+
 def cmd_serve(a):
     """OpenAI server.  Single-GPU serving runs the engine core in its own process (the HTTP
     process only formats and streams — ``infer/mp_engine.py``); TP/PP groups and
@@ -550,6 +572,12 @@ def cmd_serve(a):
     if a.guard_url:
         from ..infer.guard import GuardClient
         moderation = GuardClient(a.guard_url).moderate_sync
+    if _serve_task(a) == "embed":            # in-process EmbeddingEngine: no engine process, KV cache or sampler
+        from ..infer.embed import engine_from_args
+        tp, tpg, ppg = _parallel(a)
+        eng = engine_from_args(a, tpg, ppg)
+        serve(eng, a.host, a.port, api_key=a.api_key, log_level=getattr(a, "uvicorn_log_level", "info"))
+        return
     tp, tpg, ppg = _parallel(a)
     if tp is None and getattr(a, "engine_process", True):
         from ..infer.mp_engine import EngineClient, PromptFormatter
@@ -596,8 +624,12 @@ def cmd_guard(a):
 
 def cmd_cache_gateway(a):
     import uvicorn
-    from ..infer.cache_gateway import create_cache_gateway, http_backend, make_store
-    app = create_cache_gateway(http_backend(a.backend, a.api_key), make_store(a.redis), a.exact_ttl, a.semantic_ttl)
+    from ..infer.cache_gateway import create_cache_gateway, endpoint_embedding, http_backend, make_store
+    kw = {}
+    if getattr(a, "embedding_url", None):        # the semantic key from a /v1/embeddings endpoint, not the n-gram hash
+        kw["embed"] = endpoint_embedding(a.embedding_url, getattr(a, "embedding_model", None), a.api_key)
+    app = create_cache_gateway(http_backend(a.backend, a.api_key), make_store(a.redis), a.exact_ttl, a.semantic_ttl,
+                               **kw)
     uvicorn.run(app, host=a.host, port=a.port)
 
 
@@ -1048,8 +1080,24 @@ def build_parser() -> argparse.ArgumentParser:
                    help="shared remote KV-chunk store (LMCache server role; `lipa kv-server`)")
     p.add_argument("--no-engine-process", dest="engine_process", action="store_false",
                    help="run the engine core in the HTTP process (default: its own process)")
+    p.add_argument("--task", default="generate", choices=["generate", "embed", "embedding"],
+                   help="embed: serve /v1/embeddings with the embedding engine (vLLM --task embed)")
+    p.add_argument("--runner", default=None, choices=["auto", "generate", "pooling"],
+                   help="vLLM 0.11's spelling: pooling = --task embed")
+    p.add_argument("--override-pooler-config", dest="override_pooler_config", default=None,
+                   help='vLLM flag, JSON: {"pooling_type": "MEAN"|"CLS"|"LAST", "normalize": bool}')
     _add_parallel_args(p)
     p.set_defaults(fn=cmd_serve)
+
+    p = sub.add_parser("embed", help="offline embeddings: prints the /v1/embeddings JSON for --input texts")
+    p.add_argument("--model", required=True, help="HF dir or random:<bert / qwen3 preset>")
+    p.add_argument("--tokenizer")
+    p.add_argument("--input", nargs="+", required=True, metavar="TEXT")
+    p.add_argument("--dimensions", type=int, default=None)
+    p.add_argument("--max-model-len", dest="max_model_len", type=int, default=None)
+    p.add_argument("--max-num-batched-tokens", dest="max_batched_tokens", type=int, default=2048)
+    p.add_argument("--override-pooler-config", dest="override_pooler_config", default=None)
+    p.set_defaults(fn=cmd_embed)
 
     p = sub.add_parser("serve-deploy", help="Ray Serve-style autoscaling replicas from a serve config (H4)")
     p.add_argument("config")
@@ -1084,6 +1132,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--redis", default=None, help="redis://host:port/db (default: in-process store)")
     p.add_argument("--exact-ttl", dest="exact_ttl", type=int, default=300)
     p.add_argument("--semantic-ttl", dest="semantic_ttl", type=int, default=600)
+    p.add_argument("--embedding-url", dest="embedding_url", default=None,
+                   help="semantic key from this OpenAI /v1/embeddings endpoint (lipa serve --task embed)")
+    p.add_argument("--embedding-model", dest="embedding_model", default=None, help="`model` sent to --embedding-url")
     p.add_argument("--host", default="0.0.0.0")
     p.add_argument("--port", type=int, default=8088)
     p.set_defaults(fn=cmd_cache_gateway)

@@ -78,7 +78,7 @@ void launch_attn_bwd(const void*, const void*, const void*, const void*, const v
                      float*, hipStream_t);
 int attn_dkv_nsplit(int, int, int, int);
 void launch_attn_varlen_fwd(const void*, const void*, const void*, int, int, int, const int*, void*, float*, int, int,
-                            int, int, int, float, hipStream_t);
+                            int, int, int, float, int, hipStream_t);
 void launch_attn_varlen_bwd(const void*, const void*, const void*, const void*, const void*, const float*, const int*,
                             int, int, int, void*, void*, void*, float*, int, int, int, int, int, float, hipStream_t);
 void attn_set_trace(void*);
@@ -149,6 +149,8 @@ bool embedding_supported(int64_t, int64_t);
 void launch_embedding_fwd(const void*, const int64_t*, void*, int64_t, int64_t, int64_t, int64_t, int*, hipStream_t);
 void launch_embedding_bwd(const void*, int, const int64_t*, float*, int64_t, int64_t, int64_t, int64_t, hipStream_t);
 void launch_dropout_bwd_add(void*, const void*, size_t, uint64_t, float, hipStream_t);
+int pool_embed_split_rows();
+void launch_pool_embed(const void*, int, long, const int*, float*, float*, int*, int, int, int, int, int, hipStream_t);
 
 namespace {
 
@@ -1149,7 +1151,7 @@ std::vector<Tensor> attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o
   return {dq, dk, dv};
 }
 
-// Packed (varlen) causal attention: q [T, hq*d], k/v [T, hkv*d] (strided views allowed), sequence b = rows
+// Packed (varlen) attention, causal (forward / backward) or bidirectional (forward only, causal = false): q [T, hq*d], k/v [T, hkv*d] (strided views allowed), sequence b = rows
 // cu_seqlens[b] .. cu_seqlens[b+1] - 1 (int32 [N+1] on the device; cu_seqlens[0] == 0 and cu_seqlens[N] == T are the
 // caller's to check, it holds the host copy).  lse is [N, hq, max_seqlen rounded up to 64], internal to the op.
 static int64_t attn_varlen_check(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu, int64_t max_seqlen,
@@ -1167,7 +1169,7 @@ static int64_t attn_varlen_check(const Tensor& q, const Tensor& k, const Tensor&
 }
 
 std::vector<Tensor> attn_varlen_fwd(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens, int64_t max_seqlen, int64_t hq,
-                                    int64_t hkv, int64_t d, double scale, double p_drop) {
+                                    int64_t hkv, int64_t d, double scale, double p_drop, bool causal) {
   TORCH_CHECK(p_drop == 0.0, "attn_varlen_fwd: attention dropout is not supported with cu_seqlens");
   const int64_t T = attn_varlen_check(q, k, v, cu_seqlens, max_seqlen, hq, hkv, d, "attn_varlen_fwd");
   const int64_t N = cu_seqlens.numel() - 1, ss = (max_seqlen + 63) / 64 * 64;
@@ -1175,7 +1177,7 @@ std::vector<Tensor> attn_varlen_fwd(Tensor q, Tensor k, Tensor v, Tensor cu_seql
   auto lse = at::empty({N, hq, ss}, q.options().dtype(at::kFloat));
   launch_attn_varlen_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
                          cu_seqlens.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(), (int)N, (int)max_seqlen,
-                         (int)hq, (int)hkv, (int)d, (float)scale, stream());
+                         (int)hq, (int)hkv, (int)d, (float)scale, causal ? 1 : 0, stream());
   return {o, lse};
 }
 
@@ -1200,6 +1202,55 @@ std::vector<Tensor> attn_varlen_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, T
                          dk.data_ptr(), dv.data_ptr(), delta.data_ptr<float>(), (int)N, (int)max_seqlen, (int)hq,
                          (int)hkv, (int)d, (float)scale, stream());
   return {dq, dk, dv};
+}
+
+// ------------------------------------------------------------------ embedding pooling
+// hidden [T, H] (bf16 / fp32, unit inner stride, 16-B aligned rows, H % 8 == 0), cu_seqlens int32 [N+1] on the
+// device, mode 0 last / 1 cls / 2 mean, dims 0 (= H) or 1..H, -> fp32 [N, dims].  cu_host is the caller's host copy
+// of cu_seqlens (int32, CPU); without it the boundaries are read back here (one sync).  Every check, the
+// boundaries' included (start at 0, non-decreasing, end at T), runs on the host before anything is launched: the
+// kernel indexes rows with what cu_seqlens holds.
+Tensor pool_embed(Tensor hidden, Tensor cu_seqlens, int64_t mode, int64_t dims, bool normalize,
+                  optional<Tensor> cu_host) {
+  TORCH_CHECK(hidden.is_cuda() && hidden.dim() == 2, "pool_embed: hidden must be a [T, H] GPU tensor");
+  const int f32 = dtype_code(hidden) == 0;
+  const int64_t T = hidden.size(0), H = hidden.size(1), el = f32 ? 4 : 2;
+  TORCH_CHECK(H > 0 && H % 8 == 0, "pool_embed: hidden size must be a multiple of 8, got ", H);
+  TORCH_CHECK(hidden.stride(1) == 1 && hidden.stride(0) >= H && (hidden.stride(0) * el) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(hidden.data_ptr()) % 16 == 0,
+              "pool_embed: hidden needs unit inner stride and 16-byte aligned rows");
+  TORCH_CHECK(cu_seqlens.is_cuda() && cu_seqlens.scalar_type() == at::kInt && cu_seqlens.dim() == 1 &&
+                  cu_seqlens.is_contiguous() && cu_seqlens.numel() >= 1,
+              "pool_embed: cu_seqlens must be a contiguous int32 [N+1] tensor on the device");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "pool_embed: mode 0 (last), 1 (cls) or 2 (mean)");
+  if (dims == 0) dims = H;
+  TORCH_CHECK(dims >= 1 && dims <= H, "pool_embed: dims must be in [1, H = ", H, "], got ", dims);
+  const int64_t N = cu_seqlens.numel() - 1;
+  TORCH_CHECK(N <= 65535, "pool_embed: at most 65535 sequences per call");
+  Tensor ch = cu_host && cu_host->defined() ? *cu_host : cu_seqlens.cpu();
+  TORCH_CHECK(!ch.is_cuda() && ch.scalar_type() == at::kInt && ch.dim() == 1 && ch.is_contiguous() &&
+                  ch.numel() == N + 1,
+              "pool_embed: cu_host must be a contiguous int32 CPU tensor of cu_seqlens' length");
+  const int* c = ch.data_ptr<int>();
+  TORCH_CHECK(c[0] == 0 && c[N] == T, "pool_embed: cu_seqlens must start at 0 and end at the token count ", T,
+              ", got ", c[0], " .. ", c[N]);
+  const int split = pool_embed_split_rows();
+  int64_t nsplit = 1;
+  for (int64_t i = 0; i < N; ++i) {
+    TORCH_CHECK(c[i + 1] >= c[i], "pool_embed: cu_seqlens must be non-decreasing");
+    if (mode == 2) nsplit = std::max<int64_t>(nsplit, ((int64_t)c[i + 1] - c[i] + split - 1) / split);
+  }
+  auto out = at::empty({N, dims}, hidden.options().dtype(at::kFloat));
+  if (N == 0) return out;
+  Tensor ws, cnt;
+  if (nsplit > 1) {
+    ws = at::empty({T / split + N + 1, (dims + 7) / 8 * 8}, out.options());
+    cnt = at::zeros({N}, out.options().dtype(at::kInt));
+  }
+  launch_pool_embed(hidden.data_ptr(), f32, (long)hidden.stride(0), cu_seqlens.data_ptr<int>(), out.data_ptr<float>(),
+                    ws.defined() ? ws.data_ptr<float>() : nullptr, cnt.defined() ? cnt.data_ptr<int>() : nullptr,
+                    (int)N, (int)dims, (int)mode, normalize ? 1 : 0, (int)nsplit, stream());
+  return out;
 }
 
 // ------------------------------------------------------------------ fused LoRA branch kernels
@@ -2068,10 +2119,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd_ext", &attn_fwd_ext);
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_varlen_fwd", &attn_varlen_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens"),
-        py::arg("max_seqlen"), py::arg("hq"), py::arg("hkv"), py::arg("d"), py::arg("scale"), py::arg("p_drop") = 0.0);
+        py::arg("max_seqlen"), py::arg("hq"), py::arg("hkv"), py::arg("d"), py::arg("scale"), py::arg("p_drop") = 0.0,
+        py::arg("causal") = true);
   m.def("attn_varlen_bwd", &attn_varlen_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("hq"), py::arg("hkv"), py::arg("d"),
         py::arg("scale"), py::arg("p_drop") = 0.0);
+  m.def("pool_embed", &pool_embed, py::arg("hidden"), py::arg("cu_seqlens"), py::arg("mode"), py::arg("dims") = 0,
+        py::arg("normalize") = true, py::arg("cu_host") = py::none());
+  m.def("pool_embed_split_rows", &pool_embed_split_rows);
   // debug: phase timestamps of the D = 128 dK/dV kernel go into `buf` (u8/i64 tensor) while set; None clears
   m.def("attn_set_trace", [](optional<Tensor> buf) { attn_set_trace(buf && buf->defined() ? buf->data_ptr() : nullptr); });
   m.def("car_alloc", &car_alloc_py);

@@ -1591,16 +1591,21 @@ void launch_attn_bwd(const void* dout, const void* q, const void* k, const void*
 // cu_seqlens[b] .. cu_seqlens[b+1] - 1 (int32, device), max_seqlen on the host sizes the block axis.  The same
 // kernel bodies (VL = true) with cu_seqlens in the kv_lens slot and max_seqlen as S: the grid's batch axis is
 // the sequence, every bound is the sequence's own length, a workgroup past its sequence's end returns at once.
-// Causal, no dropout, no q_offs / kv_lens, key blocks never split.  lse / delta are [N, hq, sstride], sstride =
+// No dropout, no q_offs / kv_lens, key blocks never split.  lse / delta are [N, hq, sstride], sstride =
 // max_seqlen rounded up to 64 (the kernels derive it from S): the dK/dV kernel's 16-B lse / delta loads stay
 // aligned whatever cu_seqlens holds.
+// The forward is causal or bidirectional (encoders).  With causal = 0 the sequence's own length is the only bound
+// on the keys a query reads (VL sets Skv = kvlen = L): kend = L ends the key loop, need_mask fires on the tile
+// that holds key L (k0 + 64 > kvlen) and klim = L - 1 cuts it there; rows past L come in as the sequence's last
+// row (attn_fwd_k) or as zeros (attn_fwd128_k's range-checked DMA), never as the neighbour's.  The grid runs in the
+// plain XCD order: longest-first has no diagonal to balance.  The backward stays causal only.
 void launch_attn_varlen_fwd(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
                             const int* cu_seqlens, void* o, float* lse, int N, int max_seqlen, int hq, int hkv,
-                            int D, float scale, hipStream_t st) {
+                            int D, float scale, int is_causal, hipStream_t st) {
   const DropParams dp = make_drop(0.f, 0);
   dim3 grid((max_seqlen + 127) / 128, hq, N), blk(256);
   const float sl2 = scale * LOG2E;
-  const int causal = 1 | (attn_lpt() << 1);
+  const int causal = is_causal ? 1 | (attn_lpt() << 1) : 0;
   if (D == 128) {
     attn_fwd128_k<false, true><<<grid, blk, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, ldq, ldk, ldv,
                                                      cu_seqlens, nullptr, (bf16*)o, lse, max_seqlen, max_seqlen,

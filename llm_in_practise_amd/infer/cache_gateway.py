@@ -137,6 +137,31 @@ def create_cache_gateway(backend: Callable[[str, dict], dict], store=None, exact
     return app
 
 
+def endpoint_embedding(url: str, model: str | None = None, api_key: str | None = None, timeout: float = 60.0,
+                       post: Callable[[str, dict], dict] | None = None) -> Callable[[str], list[float]]:
+    """``text -> vector`` from an OpenAI ``/v1/embeddings`` endpoint (``lipa serve --task embed``; the
+    ``embedding-engine`` of the reference's semantic-cache compose file) for ``create_cache_gateway(embed=...)``.
+    ``url`` is the server's base URL or the full ``.../v1/embeddings`` URL; ``post(url, body) -> dict`` replaces
+    the HTTP call (tests)."""
+    full = url.rstrip("/")
+    if not full.endswith("/embeddings"):
+        full += "/embeddings" if full.endswith("/v1") else "/v1/embeddings"
+    if post is None:
+        import httpx
+        client = httpx.Client(timeout=timeout)
+        headers = {"Authorization": f"Bearer {api_key}"} if api_key else {}
+
+        def post(u: str, body: dict) -> dict:
+            r = client.post(u, json=body, headers=headers)
+            r.raise_for_status()
+            return r.json()
+
+    def embed(text: str) -> list[float]:
+        body = {"input": text or " ", **({"model": model} if model else {})}
+        return [float(x) for x in post(full, body)["data"][0]["embedding"]]
+    return embed
+
+
 def http_backend(base_url: str, api_key: str | None = None, timeout: float = 600.0):
     """Upstream caller for :func:`create_cache_gateway` (any OpenAI-compatible server)."""
     import httpx

@@ -519,6 +519,10 @@ def create_router_app(router: Router, scrape: bool = True) -> FastAPI:
     async def completions(request: Request):
         return await handle("/completions", request)
 
+    @app.post("/v1/embeddings")
+    async def embeddings(request: Request):      # the `aembedding` route of the LiteLLM configs (non-streaming)
+        return await handle("/embeddings", request)
+
     @app.get("/v1/models")
     async def models():
         return {"object": "list", "data": [{"id": g, "object": "model", "owned_by": "lipa-router"}

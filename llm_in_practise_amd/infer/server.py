@@ -11,7 +11,9 @@ with Pydantic request/response models, ``chatcmpl-<uuid>`` ids, a system message
 * optional pre-call moderation (LiteLLM ``guardrails: openai_moderation pre_call``,
   ``litellm-config-with-guard-model.yaml:24-33``): flagged input → HTTP 400 with the moderation
   result;
-* optional ``X-API-KEY`` / ``Authorization: Bearer`` auth.
+* optional ``X-API-KEY`` / ``Authorization: Bearer`` auth;
+* ``POST /v1/embeddings`` on a ``--task embed`` server (:class:`~llm_in_practise_amd.infer.embed.EmbeddingEngine`);
+  a generate server refuses it, an embed server refuses the two generation endpoints (HTTP 400, as vLLM).
 
 Generation runs on the :class:`~llm_in_practise_amd.infer.engine.ServingEngine` worker
 (continuous batching: requests join and leave the running decode batch every iteration).
@@ -19,10 +21,12 @@ Generation runs on the :class:`~llm_in_practise_amd.infer.engine.ServingEngine` 
 from __future__ import annotations
 
 import asyncio
+import base64
 import json
+import struct
 import time
 import uuid
-from typing import Literal, Optional, Union
+from typing import Any, Literal, Optional, Union
 
 from fastapi import FastAPI, HTTPException, Request
 from fastapi.responses import JSONResponse, PlainTextResponse, StreamingResponse
@@ -76,6 +80,18 @@ class CompletionRequest(BaseModel):
     min_p: float = 0.0
     seed: Optional[int] = None
     logit_bias: Optional[dict[Union[int, str], float]] = None   # token id (JSON object keys are strings) -> bias
+
+
+class EmbeddingRequest(BaseModel):
+    """OpenAI ``/v1/embeddings`` + vLLM's ``truncate_prompt_tokens``.  ``input`` is a string, a list of strings, a
+    list of token ids or a list of token-id lists; its shape is checked by hand so that a bad one is a 400 that
+    names the field."""
+    model: Optional[str] = None
+    input: Any = None
+    encoding_format: str = "float"
+    dimensions: Optional[int] = None
+    user: Optional[str] = None
+    truncate_prompt_tokens: Optional[int] = None
 
 
 class ChoiceMessage(BaseModel):
@@ -149,6 +165,55 @@ def _params(req, max_logprobs: int = 20, vocab_size: int | None = None) -> Sampl
     return SamplingParams(max_tokens=req.max_tokens, temperature=req.temperature, top_p=req.top_p, top_k=req.top_k,
                           repetition_penalty=req.repetition_penalty, stop=stop,
                           ignore_eos=req.ignore_eos, logprobs=k, **_row_params(req, vocab_size))
+
+
+def _is_ids(x) -> bool:
+    return isinstance(x, list) and all(isinstance(t, int) and not isinstance(t, bool) for t in x)
+
+
+def _embedding_inputs(req: EmbeddingRequest, engine) -> list[list[int]]:
+    """The request's inputs as validated token-id lists (HTTP 400 naming the field otherwise)."""
+    x = req.input
+    if isinstance(x, str):
+        items = [x]
+    elif isinstance(x, list) and x and _is_ids(x):
+        items = [x]
+    elif isinstance(x, list) and x and all(isinstance(i, str) for i in x):
+        items = x
+    elif isinstance(x, list) and x and all(_is_ids(i) for i in x):
+        items = x
+    elif x is None or x == [] or x == "":
+        _bad("input", "must not be empty")
+    else:
+        _bad("input", "must be a string, a list of strings, a list of token ids or a list of token-id lists")
+    k = req.truncate_prompt_tokens
+    if k is not None:
+        if k == -1:
+            k = engine.max_model_len
+        if not 1 <= k <= engine.max_model_len:
+            _bad("truncate_prompt_tokens", f"must be -1 or in [1, {engine.max_model_len}]")
+    out = []
+    for i, it in enumerate(items):
+        if isinstance(it, str):
+            if not it:
+                _bad("input", f"item {i} is empty")
+            try:
+                ids = engine.tokenize(it)
+            except ValueError as e:
+                _bad("input", str(e))
+        else:
+            ids = list(it)
+        if not ids:
+            _bad("input", f"item {i} is empty")
+        if min(ids) < 0 or max(ids) >= engine.vocab_size:
+            _bad("input", f"item {i}: token id outside the vocabulary [0, {engine.vocab_size})")
+        if k is not None:
+            ids = ids[-k:]                       # vLLM keeps the last k tokens
+        if len(ids) > engine.max_model_len:
+            _bad("input", f"item {i}: {len(ids)} tokens exceed the model's limit of {engine.max_model_len} "
+                          "(set truncate_prompt_tokens to cut it)")
+        out.append(ids)
+    return out
 
 
 def _tokenizer(engine):
@@ -248,8 +313,41 @@ def create_app(engine: ServingEngine, api_key: str | None = None, moderation=Non
     async def metrics():
         return PlainTextResponse(engine.prometheus(), media_type="text/plain; version=0.0.4")
 
+    embedder = getattr(engine, "task", "generate") == "embed"
+
+    def _unsupported(api: str):
+        raise HTTPException(status_code=400, detail=f"the model does not support the {api} API")
+
+    @app.post("/v1/embeddings")
+    async def embeddings(req: EmbeddingRequest):
+        if not embedder:
+            _unsupported("Embeddings")
+        if req.encoding_format not in ("float", "base64"):
+            _bad("encoding_format", "must be 'float' or 'base64'")
+        dims = req.dimensions
+        if dims is not None:
+            if not 1 <= dims <= engine.hidden_size:
+                _bad("dimensions", f"must be in [1, {engine.hidden_size}]")
+            if not engine.dims_allowed(dims):
+                _bad("dimensions", "the model does not support matryoshka dimensions "
+                                   "(config.json: is_matryoshka / matryoshka_dimensions)")
+        inputs = _embedding_inputs(req, engine)
+        try:
+            futs = [engine.submit(ids, dims) for ids in inputs]
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        vecs = await asyncio.gather(*[asyncio.wrap_future(f) for f in futs])
+        if req.encoding_format == "base64":     # little-endian float32 bytes
+            vecs = [base64.b64encode(struct.pack(f"<{len(v)}f", *v)).decode("ascii") for v in vecs]
+        n = sum(len(i) for i in inputs)
+        return {"object": "list", "model": req.model or engine.model_name,
+                "data": [{"object": "embedding", "index": i, "embedding": v} for i, v in enumerate(vecs)],
+                "usage": {"prompt_tokens": n, "total_tokens": n}}
+
     @app.post("/v1/chat/completions")
     async def chat(req: ChatCompletionRequest):
+        if embedder:
+            _unsupported("Chat Completions")
         msgs = [m.model_dump() for m in req.messages]
         await _moderate("\n".join(m["content"] for m in msgs if m["role"] == "user"))
         prompt = engine.build_chat_prompt(msgs)
@@ -274,6 +372,8 @@ def create_app(engine: ServingEngine, api_key: str | None = None, moderation=Non
 
     @app.post("/v1/completions")
     async def completions(req: CompletionRequest):
+        if embedder:
+            _unsupported("Completions")
         await _moderate(req.prompt)
         cid, created = "cmpl-" + uuid.uuid4().hex, int(time.time())
         name = req.model or engine.model_name

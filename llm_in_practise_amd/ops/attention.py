@@ -14,8 +14,9 @@ suffix prefill: ``Sq`` new queries per row at absolute positions ``q_offs[b] + i
 of ``Skv`` rows (``Fine-Tuning/README.md`` vLLM APC / chunked prefill parity).
 
 :func:`flash_attention_varlen` is the packed form (FlashAttention-varlen contract): ``N`` sequences back to
-back in ``[T, H*D]``, boundaries in ``cu_seqlens [N+1]``; causal, attention never crosses a boundary (neat
-sample packing for SFT, the serving engine's packed prefill).
+back in ``[T, H*D]``, boundaries in ``cu_seqlens [N+1]``; attention never crosses a boundary.  Causal (neat sample
+packing for SFT, the serving engine's packed prefill) or, forward only, bidirectional (``causal=False``: packed
+encoders, the embedding engine).
 
 The kernel returns the per-row log-sum-exp so the backward recomputes P instead of storing the
 S×S matrix.
@@ -121,11 +122,16 @@ def check_cu_seqlens(cu, total: int, max_seqlen: int | None = None) -> list[int]
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens: torch.Tensor, max_seqlen: int, hq: int, hkv: int, d: int,
-                           scale: float | None = None, cu_host=None, dropout_p: float = 0.0) -> torch.Tensor:
-    """Causal attention over ``N`` packed sequences: ``q [T, Hq*D]``, ``k/v [T, Hkv*D]`` (strided views allowed),
+                           scale: float | None = None, cu_host=None, dropout_p: float = 0.0,
+                           causal: bool = True) -> torch.Tensor:
+    """Attention over ``N`` packed sequences: ``q [T, Hq*D]``, ``k/v [T, Hkv*D]`` (strided views allowed),
     sequence ``b`` = rows ``cu_seqlens[b] .. cu_seqlens[b+1] - 1`` (int32), ``max_seqlen`` ≥ the longest one.
     ``cu_host`` is an already validated host copy of ``cu_seqlens`` (list); without it the boundaries are read
-    back and checked here (one device sync).  Zero-length sequences are legal."""
+    back and checked here (one device sync).  Zero-length sequences are legal.  ``causal=False`` is the
+    bidirectional (encoder) form: every query sees every key of its own sequence; it is forward only."""
+    if not causal and torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise NotImplementedError("flash_attention_varlen(causal=False) has no backward: run it under "
+                                  "torch.no_grad() or on inputs that do not require grad")
     if dropout_p:
         raise ValueError("flash_attention_varlen: attention dropout is not supported with cu_seqlens")
     if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1:
@@ -137,12 +143,15 @@ def flash_attention_varlen(q, k, v, cu_seqlens: torch.Tensor, max_seqlen: int, h
     if native_ok(q, d):
         if not (_aligned(q, d) and _aligned(k, d) and _aligned(v, d)):
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if not causal:      # forward only (checked above): never enters _FlashAttnVarlenFn and its causal backward
+            return native().attn_varlen_fwd(q.detach(), k.detach(), v.detach(), cu_seqlens.to(q.device),
+                                            int(max_seqlen), hq, hkv, d, scale, 0.0, False)[0]
         return fn_apply(_FlashAttnVarlenFn, q, k, v, cu_seqlens.to(q.device), int(max_seqlen), hq, hkv, d, scale)
     outs = []
     for a, b in zip(cu_host, cu_host[1:]):
         if b > a:
             o = ref.attention(q[a:b].reshape(1, b - a, hq, d), k[a:b].reshape(1, b - a, hkv, d),
-                              v[a:b].reshape(1, b - a, hkv, d), causal=True, scale=scale)
+                              v[a:b].reshape(1, b - a, hkv, d), causal=causal, scale=scale)
             outs.append(o.reshape(b - a, hq * d))
     return torch.cat(outs, 0) if outs else q.new_zeros(0, hq * d)
 

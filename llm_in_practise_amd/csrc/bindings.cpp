@@ -98,15 +98,6 @@ int lora_acc_chunks(int M, int K);
 void launch_lora_proj2(const void*, int, const void*, const void*, int, int, int, float*, int, void*, int, int, uint64_t, float, float,
                        uint64_t, float, float, size_t, uint8_t*, float*, hipStream_t);
 int lora_proj2_ws_floats(int, int);
-void launch_lora_proj_pair(const void*, const void*, int, const void*, const void*, int, int, int, float*, float*, float,
-                           float, int, hipStream_t);
-void launch_lora_acc_pair(const float*, const float*, int, int, const void*, const void*, int, int, int, float*, float*,
-                          int, hipStream_t);
-void launch_lora_acc_quad(const float* const[4], const int[4], const void* const[4], const int[4], const int[4],
-                          float* const[4], const int64_t[4], const int64_t[4], const float[4], const uint8_t* const[4],
-                          int, int, hipStream_t);
-void launch_lora_dA_pair(const float*, const float*, int, int, const void*, int, int, float*, float*, int64_t, int64_t,
-                         int64_t, int64_t, const uint8_t*, const uint8_t*, float, float, int, hipStream_t);
 void launch_lora_acc_jobs(int, const float* const*, const int*, const int*, const void* const*, const int*, const int*,
                           float* const*, const int64_t*, const int64_t*, const float*, const uint8_t* const*, int,
                           hipStream_t);
@@ -1289,7 +1280,7 @@ static uint8_t* keep_bits_ptr(const optional<Tensor>& m, int64_t M, int64_t K, c
   return m->data_ptr<uint8_t>();
 }
 
-// masks (optional, uint8 [2, M, K/8]): the two branches' dropout keep bits, written for the backward (lora_acc_quad, gemm4w_loradx, lora_dx2)
+// masks (optional, uint8 [2, M, K/8]): the two branches' dropout keep bits, written for the backward (lora_acc_jobs, gemm4w_loradx, lora_dx2)
 Tensor lora_proj2(Tensor x, Tensor a0, Tensor a1, optional<Tensor> outb, bool want_f32, double p0, int64_t key0,
                   double scale0, double p1, int64_t key1, double scale1, optional<Tensor> masks) {
   CHECK_BF16(x);
@@ -1397,108 +1388,6 @@ void lora_acc(Tensor g, Tensor x, int64_t c0, int64_t K, Tensor out, bool out_tr
     if (out_transposed) out.add_(s.t());
     else out.add_(s);
   }
-}
-
-// backward of a q_proj + v_proj pair, one launch per product:
-//   g_i = s_i · dy[:, c0_i : c0_i + n_i] · B_i   (B_i passed as Bᵀ [r, n_i] bf16) -> fp32 [M, r]
-std::vector<Tensor> lora_proj_pair(Tensor dy, int64_t c0a, Tensor bta, double sa, int64_t c0b, Tensor btb, double sb) {
-  CHECK_BF16(dy);
-  CHECK_BF16(bta);
-  CHECK_BF16(btb);
-  TORCH_CHECK(dy.dim() == 2 && dy.stride(1) == 1 && dy.stride(0) % 8 == 0 && c0a % 8 == 0 && c0b % 8 == 0,
-              "lora_proj_pair: dy layout");
-  TORCH_CHECK(bta.is_contiguous() && btb.is_contiguous() && bta.size(0) == btb.size(0) && bta.size(0) <= 16 &&
-                  bta.size(1) % 512 == 0 && btb.size(1) % 512 == 0 && c0a + bta.size(1) <= dy.size(1) &&
-                  c0b + btb.size(1) <= dy.size(1),
-              "lora_proj_pair: Bt_i [r, n_i % 512] within dy");
-  const int M = dy.size(0), r = bta.size(0);
-  Tensor ga = at::empty({M, r}, dy.options().dtype(at::kFloat)), gb = at::empty({M, r}, dy.options().dtype(at::kFloat));
-  const char* base = (const char*)dy.data_ptr();
-  launch_lora_proj_pair(base + c0a * 2, base + c0b * 2, dy.stride(0), bta.data_ptr(), btb.data_ptr(), r, bta.size(1),
-                        btb.size(1), ga.data_ptr<float>(), gb.data_ptr<float>(), (float)sa, (float)sb, M, stream());
-  return {ga, gb};
-}
-
-//   dB_i [n_i, r] += (dy[:, c0_i : c0_i + n_i])ᵀ · xa_i   (xa_i fp32 [M, r], one row stride for both)
-void lora_acc_pair(Tensor xa, Tensor xb, Tensor dy, int64_t c0a, Tensor outa, int64_t c0b, Tensor outb) {
-  for (const Tensor* g : {&xa, &xb})
-    TORCH_CHECK(g->scalar_type() == at::kFloat && g->dim() == 2 && g->stride(1) == 1 && g->size(1) <= 8 &&
-                    g->stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
-                "lora_acc_pair: xa fp32 [M, r<=8], 16-B aligned rows");
-  TORCH_CHECK(xa.stride(0) == xb.stride(0) && xa.size(1) == xb.size(1), "lora_acc_pair: one layout for both xa");
-  CHECK_BF16(dy);
-  TORCH_CHECK(dy.stride(1) == 1 && dy.stride(0) % 8 == 0 && c0a % 8 == 0 && c0b % 8 == 0, "lora_acc_pair: dy layout");
-  const int M = dy.size(0), r = xa.size(1);
-  for (const Tensor* o : {&outa, &outb})
-    TORCH_CHECK(o->scalar_type() == at::kFloat && o->is_contiguous() && o->dim() == 2 && o->size(1) == r &&
-                    o->size(0) % 128 == 0, "lora_acc_pair: out fp32 [n_i % 128, r] contiguous");
-  TORCH_CHECK(xa.size(0) == M && xb.size(0) == M && c0a + outa.size(0) <= dy.size(1) &&
-                  c0b + outb.size(0) <= dy.size(1), "lora_acc_pair: shapes");
-  const char* base = (const char*)dy.data_ptr();
-  launch_lora_acc_pair(xa.data_ptr<float>(), xb.data_ptr<float>(), xa.stride(0), r, base + c0a * 2, base + c0b * 2,
-                       dy.stride(0), outa.size(0), outb.size(0), outa.data_ptr<float>(), outb.data_ptr<float>(), M,
-                       stream());
-}
-
-//   dA_i [r, K] += D_i(x)ᵀ-weighted G_i (keep bits from lora_proj2, masks [2, M, K/8])
-void lora_dA_pair(Tensor g0, Tensor g1, Tensor x, Tensor out0, Tensor out1, Tensor masks, double p0, double p1) {
-  for (const Tensor* g : {&g0, &g1})
-    TORCH_CHECK(g->scalar_type() == at::kFloat && g->dim() == 2 && g->stride(1) == 1 && g->size(1) <= 8 &&
-                    g->stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
-                "lora_dA_pair: g fp32 [M, r<=8], 16-B aligned rows");
-  TORCH_CHECK(g0.stride(0) == g1.stride(0) && g0.size(1) == g1.size(1), "lora_dA_pair: one layout for both g");
-  CHECK_BF16(x);
-  const int M = x.size(0), K = x.size(1), r = g0.size(1);
-  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && K % 128 == 0, "lora_dA_pair: x layout");
-  for (const Tensor* o : {&out0, &out1})
-    TORCH_CHECK(o->scalar_type() == at::kFloat && o->dim() == 2 && o->size(0) == r && o->size(1) == K,
-                "lora_dA_pair: out fp32 [r, K]");
-  const uint8_t* kb = keep_bits_ptr(masks, M, K, "lora_dA_pair");
-  TORCH_CHECK(kb, "lora_dA_pair: keep bits required");
-  const size_t plane = (size_t)M * (K / 8);
-  launch_lora_dA_pair(g0.data_ptr<float>(), g1.data_ptr<float>(), g0.stride(0), r, x.data_ptr(), x.stride(0), K,
-                      out0.data_ptr<float>(), out1.data_ptr<float>(), out0.stride(0), out0.stride(1), out1.stride(0),
-                      out1.stride(1), p0 > 0 ? kb : nullptr, p1 > 0 ? kb + plane : nullptr,
-                      p0 > 0 ? (float)(1.0 / (1.0 - p0)) : 1.f, p1 > 0 ? (float)(1.0 / (1.0 - p1)) : 1.f, M, stream());
-}
-
-// dB_q, dB_v (as lora_acc_pair) and dA_q, dA_v (as lora_dA_pair) in one launch
-void lora_acc_quad(Tensor xa, Tensor xb, Tensor dy, int64_t c0a, Tensor outa, int64_t c0b, Tensor outb, Tensor g0,
-                   Tensor g1, Tensor x, Tensor out0, Tensor out1, Tensor masks, double p0, double p1) {
-  for (const Tensor* g : {&xa, &xb, &g0, &g1})
-    TORCH_CHECK(g->scalar_type() == at::kFloat && g->dim() == 2 && g->stride(1) == 1 && g->size(1) <= 8 &&
-                    g->stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(g->data_ptr()) % 16 == 0,
-                "lora_acc_quad: xa / g fp32 [M, r<=8], 16-B aligned rows");
-  const int r = xa.size(1);
-  TORCH_CHECK(xb.size(1) == r && g0.size(1) == r && g1.size(1) == r, "lora_acc_quad: one rank");
-  CHECK_BF16(dy);
-  CHECK_BF16(x);
-  TORCH_CHECK(dy.stride(1) == 1 && dy.stride(0) % 8 == 0 && c0a % 8 == 0 && c0b % 8 == 0, "lora_acc_quad: dy layout");
-  const int M = dy.size(0), K = x.size(1);
-  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && K % 128 == 0 && x.size(0) == M, "lora_acc_quad: x layout");
-  for (const Tensor* o : {&outa, &outb})
-    TORCH_CHECK(o->scalar_type() == at::kFloat && o->is_contiguous() && o->dim() == 2 && o->size(1) == r &&
-                    o->size(0) % 128 == 0, "lora_acc_quad: dB fp32 [n_i % 128, r] contiguous");
-  for (const Tensor* o : {&out0, &out1})
-    TORCH_CHECK(o->scalar_type() == at::kFloat && o->dim() == 2 && o->size(0) == r && o->size(1) == K,
-                "lora_acc_quad: dA fp32 [r, K]");
-  TORCH_CHECK(xa.size(0) == M && xb.size(0) == M && g0.size(0) == M && g1.size(0) == M &&
-                  c0a + outa.size(0) <= dy.size(1) && c0b + outb.size(0) <= dy.size(1), "lora_acc_quad: shapes");
-  const uint8_t* kbits = keep_bits_ptr(masks, M, K, "lora_acc_quad");
-  TORCH_CHECK(kbits, "lora_acc_quad: keep bits required");
-  const size_t plane = (size_t)M * (K / 8);
-  const char* base = (const char*)dy.data_ptr();
-  const float* G[4] = {xa.data_ptr<float>(), xb.data_ptr<float>(), g0.data_ptr<float>(), g1.data_ptr<float>()};
-  const int ldg[4] = {(int)xa.stride(0), (int)xb.stride(0), (int)g0.stride(0), (int)g1.stride(0)};
-  const void* X[4] = {base + c0a * 2, base + c0b * 2, x.data_ptr(), x.data_ptr()};
-  const int ldx[4] = {(int)dy.stride(0), (int)dy.stride(0), (int)x.stride(0), (int)x.stride(0)};
-  const int Ks[4] = {(int)outa.size(0), (int)outb.size(0), K, K};
-  float* out[4] = {outa.data_ptr<float>(), outb.data_ptr<float>(), out0.data_ptr<float>(), out1.data_ptr<float>()};
-  const int64_t sj[4] = {1, 1, out0.stride(0), out1.stride(0)};
-  const int64_t sk[4] = {r, r, out0.stride(1), out1.stride(1)};
-  const float ds[4] = {1.f, 1.f, p0 > 0 ? (float)(1.0 / (1.0 - p0)) : 1.f, p1 > 0 ? (float)(1.0 / (1.0 - p1)) : 1.f};
-  const uint8_t* kb[4] = {nullptr, nullptr, p0 > 0 ? kbits : nullptr, p1 > 0 ? kbits + plane : nullptr};
-  launch_lora_acc_quad(G, ldg, X, ldx, Ks, out, sj, sk, ds, kb, r, M, stream());
 }
 
 // ---- 1-4 adapters of one projection (the general multi-adapter path; BASELINE #2's q, k, v and o) ----
@@ -2068,10 +1957,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_proj", &lora_proj);
   m.def("lora_acc", &lora_acc);
   m.def("lora_proj2", &lora_proj2);
-  m.def("lora_proj_pair", &lora_proj_pair);
-  m.def("lora_acc_pair", &lora_acc_pair);
-  m.def("lora_dA_pair", &lora_dA_pair);
-  m.def("lora_acc_quad", &lora_acc_quad);
   m.def("lora_dx2", &lora_dx2);
   m.def("lora_proj_m", &lora_proj_m);
   m.def("int4_dequant", &int4_dequant);

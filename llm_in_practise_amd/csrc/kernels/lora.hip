@@ -99,22 +99,6 @@ __global__ __launch_bounds__(NW * 64) void lora_proj_k(const bf16* __restrict__ 
   lora_proj_body<NW, RW>(X, ldx, W, r, K, outf, ldof, outb, ldob, M, key, thr16, dscale, scale, mask_ld, blockIdx.x);
 }
 
-// two independent projections of one launch (blockIdx.y = branch): the backward's s·dy_i·B_i of
-// q_proj and v_proj, each over its own column range of dy — one launch, one tail
-struct ProjPair {
-  const bf16* X[2];
-  const bf16* W[2];
-  float* out[2];
-  int K[2];
-  float scale[2];
-};
-template <int NW, int RW>
-__global__ __launch_bounds__(NW * 64) void lora_proj_pair_k(ProjPair p, int ldx, int r, int M) {
-  const int b = blockIdx.y;
-  lora_proj_body<NW, RW>(p.X[b], ldx, p.W[b], r, p.K[b], p.out[b], r, nullptr, 0, M, 0, 0u, 1.f, p.scale[b], 0,
-                         blockIdx.x);
-}
-
 // NRL row-lanes × 64 k-threads (8 consecutive k each); a chunk of ROWS rows is walked in passes of
 // NRL·RB rows (RB rows per thread), the next pass's x / dx rows loaded before the current pass is
 // used (one exposed HBM round trip per workgroup, not one per pass); the chunk's G rows are staged
@@ -344,32 +328,13 @@ __global__ __launch_bounds__(256) void lora_acc_mfma_k(const float* __restrict__
                                   blockIdx.x, blockIdx.y);
 }
 
-// dB_i [n_i, r] += (dy[:, c0_i : c0_i + n_i])ᵀ · xa_i for two branches in one launch (the k-blocks of
-// branch 1 follow those of branch 0 along blockIdx.x)
-struct AccPair {
-  const float* G[2];
-  const bf16* X[2];
-  float* out[2];
-  int K[2];
-  int nblk0;
-  int64_t sj[2], sk[2];
-  float ds[2];            // dropout rescale 1/(1-p) (1: no dropout)
-  const uint8_t* kb[2];   // keep bits [M, K/8] (null: no dropout)
-};
-template <int SUB>
-__global__ __launch_bounds__(256) void lora_acc_pair_k(AccPair a, int ldg, int r, int ldx, int M) {
-  const int b = (int)blockIdx.x >= a.nblk0;
-  const int bx = blockIdx.x - (b ? a.nblk0 : 0);
-  lora_acc_mfma_body<8, false, SUB>(a.G[b], ldg, r, a.X[b], ldx, nullptr, 0, nullptr, a.K[b], a.out[b], a.sj[b],
-                                    a.sk[b], M, 0, a.kb[b] ? 1u : 0u, a.ds[b], 0, bx, blockIdx.y, a.kb[b]);
-}
-
-// The q+v backward's four weight-gradient products in ONE launch (job = blockIdx.x range): dB_q, dB_v
-// (dy column blocks × the forward's xa) and dA_q, dA_v (x with the stored keep bits × g) — the same
-// MFMA body as lora_acc_pair_k, each job with its own operands and strides; one launch, one tail
-// (two back-to-back launches of ≈10 µs each left half of each launch's last wave of workgroups idle).
-// The general form (AccJobs, up to 8 jobs, rank per job) serves the multi-adapter backward as well: all
-// dB and dA products of a projection's 1-4 adapters (BASELINE #2: q, k, v on q|k|v and o) in one launch.
+// Up to 8 weight-gradient products out_j += G_jᵀ·D_j(X_j) in ONE launch of lora_acc_mfma_body (job = blockIdx.x
+// range, the k-blocks of job j + 1 following those of job j), each job with its own operands, rank, strides,
+// keep bits [M, K/8] (null: no dropout) and dropout rescale ds = 1/(1-p) (1: none).  The q+v backward's four
+// products — dB_q, dB_v (dy column blocks × the forward's xa) and dA_q, dA_v (x with the stored keep bits × g) —
+// go through one launch, one tail (two back-to-back launches of ≈10 µs each left half of each launch's last
+// wave of workgroups idle), and so do all dB and dA products of a projection's 1-4 adapters in the
+// multi-adapter backward (BASELINE #2: q, k, v on q|k|v and o).
 // (Grouping the dA jobs that share x so that one workgroup loads each x tile once for all members measured
 // slower at BASELINE #2's shapes: q|k|v 45 -> 62 µs — a third of the workgroups, and the re-reads of x hit
 // the MALL anyway; profiles/r4/lora_multi_adapter.txt.)
@@ -1221,46 +1186,9 @@ void launch_lora_apply(void* Y, int ldy, int M, int nb, const float* const* xa, 
   LIPA_CHECK_LAUNCH();
 }
 
-// the backward's two-branch projections g_i = s_i·dy[:, c0_i : c0_i + K_i]·B_i (fp32 [M, r]), B_i given as
-// Bᵀ [r, K_i]; both branches have the same rank r
-void launch_lora_proj_pair(const void* X0, const void* X1, int ldx, const void* W0, const void* W1, int r, int K0,
-                           int K1, float* out0, float* out1, float s0, float s1, int M, hipStream_t st) {
-  ProjPair p{{(const bf16*)X0, (const bf16*)X1}, {(const bf16*)W0, (const bf16*)W1}, {out0, out1}, {K0, K1}, {s0, s1}};
-  // (a split-K form like lora_proj2s_k measured slower here: 10.4 + 5.2 us slab sum vs 11.1 us)
-  const int rw = M < 4096 ? 8 : 16;
-  dim3 grid((M + rw - 1) / rw, 2);
-  if (rw == 8)
-    lora_proj_pair_k<16, 8><<<grid, 1024, 0, st>>>(p, ldx, r, M);
-  else
-    lora_proj_pair_k<16, 16><<<grid, 1024, 0, st>>>(p, ldx, r, M);
-  LIPA_CHECK_LAUNCH();
-}
-
-// dB_i [K_i, r] (row-major, i.e. out[k * r + j]) += Σ_m X_i[m, k]·G_i[m, j] for two branches, r <= 8
-void launch_lora_acc_pair(const float* G0, const float* G1, int ldg, int r, const void* X0, const void* X1, int ldx,
-                          int K0, int K1, float* out0, float* out1, int M, hipStream_t st) {
-  AccPair a{{G0, G1}, {(const bf16*)X0, (const bf16*)X1}, {out0, out1}, {K0, K1}, K0 / 128, {1, 1}, {r, r},
-            {1.f, 1.f}, {nullptr, nullptr}};
-  dim3 g(K0 / 128 + K1 / 128, (M + 127) / 128);
-  lora_acc_pair_k<1><<<g, 256, 0, st>>>(a, ldg, r, ldx, M);
-  LIPA_CHECK_LAUNCH();
-}
-
-// backward of a dropout q_proj + v_proj pair from the forward's keep bits:
-//   dA_i [r, K] += Σ_m G_i[m, j]·D_i(x)[m, k]·ds_i  (one launch, both branches, fp32 atomics)
-void launch_lora_dA_pair(const float* G0, const float* G1, int ldg, int r, const void* X, int ldx, int K, float* out0,
-                         float* out1, int64_t sj0, int64_t sk0, int64_t sj1, int64_t sk1, const uint8_t* kb0,
-                         const uint8_t* kb1, float ds0, float ds1, int M, hipStream_t st) {
-  AccPair a{{G0, G1}, {(const bf16*)X, (const bf16*)X}, {out0, out1}, {K, K}, K / 128, {sj0, sj1}, {sk0, sk1},
-            {ds0, ds1}, {kb0, kb1}};
-  dim3 g(2 * (K / 128), (M + 127) / 128);
-  lora_acc_pair_k<1><<<g, 256, 0, st>>>(a, ldg, r, ldx, M);
-  LIPA_CHECK_LAUNCH();
-}
-
-// jobs 0, 1: dB of the two branches (G = xa, X = dy column block, out [n, r] row-major);
-// jobs 2, 3: dA (G = g, X = x, out [r, K] with strides, keep bits / rescale per branch)
-// (any job count 1..8: the multi-adapter backward's dB / dA products go through the same launch)
+// 1..8 jobs out_j (strides sj over the rank, sk over k) += Σ_m G_j[m, ·]·D_j(X_j)[m, k]·ds_j, K_j % 128:
+// a dB (G = the forward's xa, X = a dy column block, out [n, r] row-major: sj = 1, sk = r) or
+// a dA (G = g, X = x, out [r, K] with its strides, keep bits / rescale per branch)
 void launch_lora_acc_jobs(int njobs, const float* const* G, const int* ldg, const int* r, const void* const* X,
                           const int* ldx, const int* K, float* const* out, const int64_t* sj, const int64_t* sk,
                           const float* ds, const uint8_t* const* kb, int M, hipStream_t st) {
@@ -1292,13 +1220,6 @@ void launch_lora_acc_jobs(int njobs, const float* const* G, const int* ldg, cons
   if (su == 2) lora_acc_jobs_k<2><<<g, 256, 0, st>>>(a, M);
   else lora_acc_jobs_k<1><<<g, 256, 0, st>>>(a, M);
   LIPA_CHECK_LAUNCH();
-}
-
-void launch_lora_acc_quad(const float* const G[4], const int ldg[4], const void* const X[4], const int ldx[4],
-                          const int K[4], float* const out[4], const int64_t sj[4], const int64_t sk[4],
-                          const float ds[4], const uint8_t* const kb[4], int r, int M, hipStream_t st) {
-  const int rr[4] = {r, r, r, r};
-  launch_lora_acc_jobs(4, G, ldg, rr, X, ldx, K, out, sj, sk, ds, kb, M, st);
 }
 
 // N adapters sharing x: split-K projection (+ every branch's keep bits), then the fixed-order slab sum
@@ -1350,6 +1271,7 @@ void launch_lora_proj_cols(int nbr, const void* const* X, int ldx, const void* c
     pm.out[b] = out[b];
     pm.scale[b] = scale[b];
   }
+  // (a split-K form like lora_proj2s_k measured slower for the q+v pair: 10.4 + 5.2 us slab sum vs 11.1 us)
   const int rw = M < 4096 ? 8 : 16;
   dim3 grid((M + rw - 1) / rw, nbr);
   if (rw == 8)

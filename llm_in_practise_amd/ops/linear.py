@@ -9,9 +9,10 @@ projection of the stack runs through.
   dequant-GEMM or one expansion per step, decode kernels).
 * LoRA kernel forms (csrc/kernels/lora.hip, gemm4w_lora.hip), one per adapter layout:
   - pair — q_proj + v_proj of rank <= 8 (the QLoRA configs): ``lora_proj2`` (both s·D(x)·Aᵀ in one pass over x,
-    keep bits stored), backward ``lora_proj_pair`` + ``lora_acc_quad`` (both dB and dA in one launch);
-  - multi — 1-4 adapters of rank 8 / 16 (BASELINE #2: q, k, v, o): ``lora_proj_m``, ``lora_proj_cols``,
-    ``lora_acc_jobs``;
+    keep bits stored);
+  - multi — 1-4 adapters of rank 8 / 16 (BASELINE #2: q, k, v, o): ``lora_proj_m``;
+    both layouts share one backward (``_batched_backward``): every g in one ``lora_proj_cols`` launch, the dB
+    and dA products in one ``lora_acc_jobs`` launch;
   - per-branch — any other rank <= 16 / 128-aligned shape: ``lora_proj`` / ``lora_acc`` per adapter;
   - general — anything else (rank > 16, odd widths, > 4 adapters): torch matmuls as an extra K-slice of the base
     GEMM.
@@ -201,7 +202,7 @@ class _FusedLinearFn(torch.autograd.Function):
                 ps = [br.dropout if training else 0.0 for br in branches]
                 keys = [next_dropout_key() if p > 0 else None for p in ps]
                 a0, a1 = bf16_view(ab[0], x.dtype), bf16_view(ab[2], x.dtype)
-                # training with dropout on both: keep the masks' bits (2 bits / element of x) for the backward (lora_acc_quad, gemm4w_loradx)
+                # training with dropout on both: keep the masks' bits (2 bits / element of x) for the backward (lora_acc_jobs, gemm4w_loradx)
                 masks = (torch.empty(2, x.shape[0], x.shape[1] // 8, dtype=torch.uint8, device=x.device)
                          if need_xa and all(k is not None for k in keys) else None)
                 xa2 = native().lora_proj2(x, a0, a1, None if xa32 is None else xa32[:, :a0.shape[0] + a1.shape[0]], True,
@@ -292,6 +293,14 @@ class _FusedLinearFn(torch.autograd.Function):
         ctx.pair = bool(branches) and fast and _pair_ok(x, branches)
         # (the forward's condition for lora_proj_m: "apply" form and the multi-adapter shapes)
         ctx.multi = bool(branches) and fast and x.is_cuda and len(branches) <= 4 and _multi_ok(x, branches)
+        r0 = branches[0].a.shape[0] if branches else 0
+        same = fast and all(br.a.shape[0] == r0 for br in branches)
+        # two same-rank adapters on 512-aligned column blocks (the pair, and what lora_proj_cols takes besides);
+        # of rank <= 8: both dB in one launch
+        ctx.cols2 = same and len(branches) == 2 and all((br.c1 - br.c0) % 512 == 0 for br in branches)
+        ctx.dB2 = ctx.cols2 and r0 <= 8
+        ctx.dx_fused = same and len(branches) <= 2 and r0 % 8 == 0   # what gemm4w_loradx takes (K % 128: fast)
+        ctx.train_m = x.shape[0] >= _MIN_M
         ctx.ab_refs = ab          # the parameters themselves: fused kernels accumulate into their .grad
         ctx.has_residual = residual is not None
         # the LoRA parameters travel as ctx.ab_refs, not through save_for_backward: under non-reentrant
@@ -307,218 +316,183 @@ class _FusedLinearFn(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, weight = saved[0], saved[1]
         nb = ctx.nb
-        ab = ctx.ab_refs
         xa_list = saved[2:2 + nb]
         dense = not isinstance(base, NF4Weight)
         dy = dy.contiguous()
-        fast = ctx.fast
+        need = ctx.needs_input_grad
+        det = deterministic()
         grads_ab = [None] * (2 * nb)
-        g_list = []
-        done_quad = None      # ((dA_0, ret), (dA_1, ret)) when lora_acc_quad already produced both dA
-
-        def dest(i):   # the optimizer-owned fp32 grad view (accumulate in place) or a fresh buffer
-            prm = ctx.ab_refs[i]
-            gr = prm.grad
-            if gr is not None and getattr(prm, "_lipa_flat_grad", False) and gr.dtype == torch.float32:
-                return gr, False
-            return torch.zeros(prm.shape, dtype=torch.float32, device=dy.device), True
-
-        if (ctx.multi and not deterministic() and ctx.bts is not None and all(t is not None for t in xa_list)
-                and (ctx.masks is not None or all(k is None for k in ctx.keys))):
-            return _multi_backward(ctx, dy, x, weight, xa_list, base, branches, dense, dest)
-        # q_proj + v_proj: both adapters' s·dy_i·B_i in one launch, both dB_i in another
-        pair_g = (fast and nb == 2 and ctx.bts is not None and ctx.bts[0].shape[0] == ctx.bts[1].shape[0]
-                  and all(bt.shape[1] % 512 == 0 for bt in ctx.bts))
-        if pair_g:
-            g_list = list(native().lora_proj_pair(dy, branches[0].c0, ctx.bts[0], branches[0].scaling,
-                                                  branches[1].c0, ctx.bts[1], branches[1].scaling))
-            xs = xa_list
-            if (ctx.needs_input_grad[6] and ctx.needs_input_grad[8] and not deterministic() and xs[0] is not None
-                    and xs[1] is not None and xs[0].stride(0) == xs[1].stride(0) and xs[0].shape[1] <= 8
-                    and all((br.c1 - br.c0) % 128 == 0 for br in branches)):
-                (o0, ret0), (o1, ret1) = dest(1), dest(3)
-                # with the dropout pair's dA due too (the keep-bit path below), both dB and both dA in ONE launch
-                quad = (ctx.pair and all(k is not None for k in ctx.keys) and ctx.masks is not None
-                        and ctx.needs_input_grad[0] and ctx.needs_input_grad[5] and ctx.needs_input_grad[7]
-                        and dy.shape[0] >= _MIN_M and x.shape[1] % 128 == 0
-                        and g_list[0].shape[1] == xs[0].shape[1])
-                if quad:
-                    (a0o, aret0), (a1o, aret1) = dest(0), dest(2)
-                    native().lora_acc_quad(xs[0], xs[1], dy, branches[0].c0, o0, branches[1].c0, o1, g_list[0],
-                                           g_list[1], x, a0o, a1o, ctx.masks, branches[0].dropout, branches[1].dropout)
-                    done_quad = ((a0o, aret0), (a1o, aret1))
-                else:
-                    native().lora_acc_pair(xs[0], xs[1], dy, branches[0].c0, o0, branches[1].c0, o1)
-                for i, (o, ret) in ((0, (o0, ret0)), (1, (o1, ret1))):
-                    if ret:
-                        grads_ab[2 * i + 1] = o.to(ab[2 * i + 1].dtype)
-                    else:
-                        _notify_grad_ready(ctx.ab_refs[2 * i + 1])
-            else:
-                for i, br in enumerate(branches):
-                    if ctx.needs_input_grad[5 + 2 * i + 1]:
-                        out, ret = dest(2 * i + 1)
-                        native().lora_acc(xa_list[i], dy, br.c0, br.c1 - br.c0, out, True, None, None, 0.0, 0,
-                                          deterministic())
-                        grads_ab[2 * i + 1] = out.to(ab[2 * i + 1].dtype) if ret else None
-                        if not ret:
-                            _notify_grad_ready(ctx.ab_refs[2 * i + 1])
-        for i, br in enumerate(branches if not pair_g else ()):
-            a, b = ab[2 * i], ab[2 * i + 1]
-            n_i = br.c1 - br.c0
-            if fast:
-                bt = ctx.bts[i] if ctx.bts is not None else bf16_view(b, dy.dtype).t().contiguous()   # [r, n_i]
-                g = native().lora_proj(dy, br.c0, n_i, bt, None, True, 0.0, 0, br.scaling)   # s·dy_i·B, fp32
-                if ctx.needs_input_grad[5 + 2 * i + 1]:
-                    out, ret = dest(2 * i + 1)                                     # dB [n_i, r] += dy_iᵀ·xa_s
-                    native().lora_acc(xa_list[i], dy, br.c0, n_i, out, True, None, None, 0.0, 0, deterministic())
-                    grads_ab[2 * i + 1] = out.to(b.dtype) if ret else None
-                    if not ret:
-                        _notify_grad_ready(ctx.ab_refs[2 * i + 1])
-            else:
-                dyi = dy[:, br.c0:br.c1]
-                g = (dyi @ bf16_view(b, dy.dtype)) * br.scaling      # [T, r]  = d(xa)
-                db = (dyi.t() @ xa_list[i]) * br.scaling             # [n, r]
-                key = ctx.keys[i]
-                xin = native().dropout_fwd(x, br.dropout, key) if key is not None else x   # regenerate drop(x)
-                grads_ab[2 * i] = (g.t() @ xin).to(a.dtype)
-                grads_ab[2 * i + 1] = db.to(b.dtype)
-            g_list.append(g)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            fold = [i for i in range(nb) if ctx.keys[i] is None]
-            ext_a = ext_b = None
-
-            def fold_ext():   # no-dropout adapters' dx terms as an extra K-slice of the dX GEMM
-                if not fold:
-                    return None, None
-                ea = _pad_cols(torch.cat([g_list[i].to(dy.dtype) for i in fold], 1))
-                eb = torch.cat([bf16_view(ab[2 * i], dy.dtype) for i in fold], 0)            # [R, K]
-                return ea, F.pad(eb, (0, 0, 0, ea.shape[1] - eb.shape[0])).t().contiguous()  # [K, Rp]
-            wb = ctx.wdq if ctx.wdq is not None else (base if not dense else weight)
-            pair_ok = (ctx.pair and all(k is not None for k in ctx.keys) and not deterministic()
-                       and ctx.needs_input_grad[5] and ctx.needs_input_grad[7])
-            if pair_ok and ctx.masks is not None and not fold and dy.shape[0] >= _MIN_M:
-                # the masked LoRA input-gradient term from the stored keep bits, inside the dX GEMM (or, for shapes
-                # gemm4w_loradx does not take, written once by lora_dx2 and added as the GEMM's C matrix); dA by
-                # lora_acc_quad above or one lora_dA_pair launch — no read-modify-write pass over dx
-                a0, a1 = bf16_view(ab[0], dy.dtype), bf16_view(ab[2], dy.dtype)
-                p0, p1 = branches[0].dropout, branches[1].dropout
-                fused_ok = wb.shape[1] % 128 == 0 and all(g.shape[1] % 8 == 0 and g.shape[1] <= 32 for g in g_list)
-                if fused_ok and isinstance(wb, torch.Tensor) and _g4w_ok(dy, wb, True):
-                    # the masked LoRA input gradient inside the dX GEMM's epilogue (no lora_dx2 matrix)
-                    _count("gemm4w")
-                    dx = native().gemm4w_loradx(dy, wb, None, 0, g_list, [a0, a1], ctx.masks, [p0, p1])
-                elif fused_ok and isinstance(wb, NF4Weight) and _w4_ok(dy, wb, True):
-                    codes, sc = wb.g4w_pack()
-                    _count("gemm4w-nf4")
-                    dx = native().gemm4w_loradx(dy, codes, sc, wb.shape[1], g_list, [a0, a1], ctx.masks, [p0, p1])
-                else:
-                    c = native().lora_dx2(g_list[0], g_list[1], a0, a1, ctx.masks, p0, p1)
-                    dx = _base_gemm_t(dy, wb, None, None, c)
-                    del c
-                if done_quad is not None:
-                    (o0, ret0), (o1, ret1) = done_quad
-                else:
-                    (o0, ret0), (o1, ret1) = dest(0), dest(2)
-                    native().lora_dA_pair(g_list[0], g_list[1], x, o0, o1, ctx.masks, p0, p1)
-                ctx.masks = None
-                for i, (o, ret) in ((0, (o0, ret0)), (1, (o1, ret1))):
-                    if ret:
-                        grads_ab[2 * i] = o.to(ab[2 * i].dtype)
-                    else:
-                        _notify_grad_ready(ctx.ab_refs[2 * i])
-                done_dA = True
-            else:
-                assert done_quad is None, "lora_acc_quad ran but the keep-bit dX path did not"
-                ext_a, ext_b = fold_ext()
-                dx = _base_gemm_t(dy, wb, ext_a, ext_b)
-                done_dA = False
+        wb = (ctx.wdq if ctx.wdq is not None else (base if not dense else weight)) if need[0] else None
+        if ctx.bts is not None and (ctx.cols2 or (ctx.multi and not det)):
+            dx = _batched_backward(ctx, dy, x, xa_list, wb, det, grads_ab)
         else:
-            done_dA = False
+            dx = _adapter_backward(ctx, dy, x, xa_list, wb, det, grads_ab)
         ctx.wdq = None
         ctx.bts = None
         ctx.masks = None
-        # dA (and, for dropout adapters outside the fused dX paths, their input-gradient term) per adapter
-        branches_acc = () if done_dA else branches
-        for i, br in enumerate(branches_acc):
-            key = ctx.keys[i]
-            if fast:   # dA += gᵀ·D(x) and (dropout branches) dx += D(g·A), one pass over x / dx
-                upd = dx if (dx is not None and key is not None) else None
-                if ctx.needs_input_grad[5 + 2 * i] or upd is not None:
-                    out, ret = dest(2 * i)
-                    native().lora_acc(g_list[i], x, 0, x.shape[1], out, False, upd,
-                                      bf16_view(ab[2 * i], dy.dtype) if upd is not None else None,
-                                      br.dropout if key is not None else 0.0, key or 0, deterministic())
-                    grads_ab[2 * i] = out.to(ab[2 * i].dtype) if (ret and ctx.needs_input_grad[5 + 2 * i]) else None
-                    if not ret and ctx.needs_input_grad[5 + 2 * i]:
-                        _notify_grad_ready(ctx.ab_refs[2 * i])
-            elif dx is not None and key is not None:   # LoRA input grad through the regenerated dropout mask
-                native().dropout_bwd_add(dx, g_list[i] @ bf16_view(ab[2 * i], dy.dtype), br.dropout, key)
         dres = dy if ctx.has_residual else None
         dw = None
-        if dense and weight is not None and ctx.needs_input_grad[2]:
+        if dense and weight is not None and need[2]:
             dw = (dy.t() @ x).to(weight.dtype)
-        dbias = dy.sum(0) if ctx.needs_input_grad[3] else None
+        dbias = dy.sum(0) if need[3] else None
         return (dx, dres, dw, dbias, None, *grads_ab)
 
 
-def _multi_backward(ctx, dy, x, weight, xa_list, base, branches, dense, dest):
-    """Backward of 1-4 adapters through the multi-adapter kernels (see ``_multi_ok``): 3 LoRA launches
-    (g, dB + dA, and the dX term when it cannot ride in the dX GEMM's prologue)."""
-    ab = ctx.ab_refs
-    nb = len(branches)
-    grads_ab = [None] * (2 * nb)
-    masks, ctx.masks = ctx.masks, None
-    ps = [br.dropout if k is not None else 0.0 for br, k in zip(branches, ctx.keys)]
+def _grad_dest(prm, device):
+    """The optimizer-owned fp32 grad view of a LoRA parameter (the kernels accumulate in place) or a fresh buffer."""
+    gr = prm.grad
+    if gr is not None and getattr(prm, "_lipa_flat_grad", False) and gr.dtype == torch.float32:
+        return gr, False
+    return torch.zeros(prm.shape, dtype=torch.float32, device=device), True
+
+
+def _grad_done(ctx, grads_ab, idx, out, fresh):
+    if fresh:
+        grads_ab[idx] = out.to(ctx.ab_refs[idx].dtype)
+    else:
+        _notify_grad_ready(ctx.ab_refs[idx])
+
+
+def _acc_jobs(ctx, jobs, grads_ab):
+    """One ``lora_acc_jobs`` launch.  A job is (index into ab, G, X, c0, k, keep-bit plane or -1, dropout p):
+    odd indices are dB_i [n_i, r] += X[:, c0:c0+k]ᵀ·G, even ones dA_i [r, K] += Gᵀ·D_i(X)."""
+    idx, gs, xs, c0s, ks, planes, ps = map(list, zip(*jobs))
+    dests = [_grad_dest(ctx.ab_refs[i], gs[0].device) for i in idx]
+    native().lora_acc_jobs(gs, xs, c0s, ks, [d[0] for d in dests], [i % 2 == 1 for i in idx], ctx.masks, planes, ps)
+    for i, (o, fresh) in zip(idx, dests):
+        _grad_done(ctx, grads_ab, i, o, fresh)
+
+
+def _dA_jobs(ctx, x, g_list):
+    """dA_i [r, K] += g_iᵀ·D_i(x) from the stored keep bits, for every trainable A."""
+    return [(2 * i, g_list[i], x, 0, x.shape[1], i, br.dropout if ctx.keys[i] is not None else 0.0)
+            for i, br in enumerate(ctx.meta[1]) if ctx.needs_input_grad[5 + 2 * i]]
+
+
+def _adapter_dB(ctx, i, xa, dy, det, grads_ab):
+    br = ctx.meta[1][i]
+    out, fresh = _grad_dest(ctx.ab_refs[2 * i + 1], dy.device)          # dB [n_i, r] += dy_iᵀ·xa_s
+    native().lora_acc(xa, dy, br.c0, br.c1 - br.c0, out, True, None, None, 0.0, 0, det)
+    _grad_done(ctx, grads_ab, 2 * i + 1, out, fresh)
+
+
+def _keep_bits_serve(ctx, det) -> bool:
+    """The forward's stored keep bits serve every dA and the dX term (else each dropout adapter regenerates its
+    mask from its key, ``lora_acc``): the multi layout always, the q+v pair at training sizes when x and both
+    A take a gradient.  (Keep bits that are not the multi layout's are the pair's, stored only when both
+    adapters have dropout: ``masks is not None and not multi`` stands for ``pair and all keys``.)"""
+    need = ctx.needs_input_grad
+    return (ctx.masks is not None and not det
+            and (ctx.multi or (need[0] and need[5] and need[7] and ctx.train_m)))
+
+
+def _batched_backward(ctx, dy, x, xa_list, wb, det, grads_ab):
+    """Backward of the pair and multi layouts (also of any two same-rank adapters on 512-aligned column blocks):
+      1. every g_i = s_i·dy_i·B_i in one launch (``lora_proj_cols``);
+      2. the weight-gradient products in one launch (``lora_acc_jobs``): the multi layout every dB and dA; two
+         adapters of rank <= 8 both dB, and both dA with them when the stored keep bits serve;
+      3. dX (``_dx_and_dA``), with whatever step 2 left to the per-adapter kernel.
+    Deterministic mode keeps step 1 (no atomics in it) and leaves dB and dA to ``lora_acc``'s fixed-order sums."""
+    branches = ctx.meta[1]
+    need = ctx.needs_input_grad
+    whole = ctx.multi and not det
+    keep = _keep_bits_serve(ctx, det)
     g_list = native().lora_proj_cols(dy, [br.c0 for br in branches], ctx.bts, [br.scaling for br in branches])
-    ctx.bts = None
-    jobs, fin = [], []
-    for i, br in enumerate(branches):
-        if ctx.needs_input_grad[5 + 2 * i + 1]:      # dB_i [n_i, r] += dy_iᵀ·xa_i
-            o, ret = dest(2 * i + 1)
-            jobs.append((xa_list[i], dy, br.c0, br.c1 - br.c0, o, True, -1, 0.0))
-            fin.append((2 * i + 1, o, ret))
-    for i, br in enumerate(branches):
-        if ctx.needs_input_grad[5 + 2 * i]:          # dA_i [r, K] += g_iᵀ·D_i(x)
-            o, ret = dest(2 * i)
-            jobs.append((g_list[i], x, 0, x.shape[1], o, False, i, ps[i]))
-            fin.append((2 * i, o, ret))
+    jobs = []
+    if whole or (ctx.dB2 and need[6] and need[8] and not det):
+        jobs = [(2 * i + 1, xa_list[i], dy, br.c0, br.c1 - br.c0, -1, 0.0)
+                for i, br in enumerate(branches) if need[6 + 2 * i]]
+    else:
+        for i in range(len(branches)):
+            if need[6 + 2 * i]:
+                _adapter_dB(ctx, i, xa_list[i], dy, det, grads_ab)
+    # (the pair's dA ride with its dB launch; with B frozen they go alone after the dX GEMM, _dx_and_dA)
+    dA_done = whole or (keep and bool(jobs))
+    if dA_done:
+        jobs += _dA_jobs(ctx, x, g_list)
     if jobs:
-        cols = list(zip(*jobs))
-        native().lora_acc_jobs(list(cols[0]), list(cols[1]), list(cols[2]), list(cols[3]), list(cols[4]),
-                               list(cols[5]), masks, list(cols[6]), list(cols[7]))
-    for idx, o, ret in fin:
-        if ret:
-            grads_ab[idx] = o.to(ab[idx].dtype)
+        _acc_jobs(ctx, jobs, grads_ab)
+    return _dx_and_dA(ctx, dy, x, wb, g_list, keep, dA_done, det, grads_ab)
+
+
+def _adapter_backward(ctx, dy, x, xa_list, wb, det, grads_ab):
+    """Backward one adapter at a time: ``lora_proj`` / ``lora_acc`` for the fused-kernel shapes, torch matmuls
+    for the general form."""
+    branches = ctx.meta[1]
+    ab = ctx.ab_refs
+    need = ctx.needs_input_grad
+    g_list = []
+    for i, br in enumerate(branches):
+        a, b = ab[2 * i], ab[2 * i + 1]
+        if ctx.fast:
+            bt = ctx.bts[i] if ctx.bts is not None else bf16_view(b, dy.dtype).t().contiguous()   # [r, n_i]
+            g = native().lora_proj(dy, br.c0, br.c1 - br.c0, bt, None, True, 0.0, 0, br.scaling)   # s·dy_i·B, fp32
+            if need[6 + 2 * i]:
+                _adapter_dB(ctx, i, xa_list[i], dy, det, grads_ab)
         else:
-            _notify_grad_ready(ab[idx])
+            dyi = dy[:, br.c0:br.c1]
+            g = (dyi @ bf16_view(b, dy.dtype)) * br.scaling      # [T, r]  = d(xa)
+            db = (dyi.t() @ xa_list[i]) * br.scaling             # [n, r]
+            key = ctx.keys[i]
+            xin = native().dropout_fwd(x, br.dropout, key) if key is not None else x   # regenerate drop(x)
+            grads_ab[2 * i] = (g.t() @ xin).to(a.dtype)
+            grads_ab[2 * i + 1] = db.to(b.dtype)
+        g_list.append(g)
+    return _dx_and_dA(ctx, dy, x, wb, g_list, _keep_bits_serve(ctx, det), False, det, grads_ab)
+
+
+def _dx_and_dA(ctx, dy, x, wb, g_list, keep, dA_done, det, grads_ab):
+    """dX = dy·W + the adapters' input-gradient term (when x takes a gradient), then the dA not yet launched."""
+    branches = ctx.meta[1]
+    ab = ctx.ab_refs
+    need = ctx.needs_input_grad
     dx = None
-    if ctx.needs_input_grad[0]:
-        wb = ctx.wdq if ctx.wdq is not None else (base if not dense else weight)
-        a_list = [bf16_view(ab[2 * i], dy.dtype) for i in range(nb)]
-        if masks is None:    # no dropout: the adapters' g·A as an extra K-slice of the dX GEMM
-            ea = _pad_cols(torch.cat([g.to(dy.dtype) for g in g_list], 1))
-            eb = torch.cat(a_list, 0)
-            dx = _base_gemm_t(dy, wb, ea, F.pad(eb, (0, 0, 0, ea.shape[1] - eb.shape[0])).t().contiguous())
+    if need[0] and keep:
+        # the masked term from the stored keep bits: inside the dX GEMM's prologue, or written once
+        # (lora_dx2 / lora_dxc) and added as the GEMM's C matrix — no read-modify-write pass over dx
+        a_list = [bf16_view(a, dy.dtype) for a in ab[0::2]]
+        ps = [br.dropout if k is not None else 0.0 for br, k in zip(branches, ctx.keys)]
+        fused = ctx.dx_fused
+        if fused and isinstance(wb, torch.Tensor) and _g4w_ok(dy, wb, True):
+            _count("gemm4w")
+            dx = native().gemm4w_loradx(dy, wb, None, 0, g_list, a_list, ctx.masks, ps)
+        elif fused and isinstance(wb, NF4Weight) and _w4_ok(dy, wb, True):
+            codes, sc = wb.g4w_pack()
+            _count("gemm4w-nf4")
+            dx = native().gemm4w_loradx(dy, codes, sc, wb.shape[1], g_list, a_list, ctx.masks, ps)
         else:
-            fused = nb <= 2 and wb.shape[1] % 128 == 0 and all(g.shape[1] == g_list[0].shape[1] for g in g_list)
-            if fused and isinstance(wb, torch.Tensor) and _g4w_ok(dy, wb, True):
-                _count("gemm4w")
-                dx = native().gemm4w_loradx(dy, wb, None, 0, g_list, a_list, masks, ps)
-            elif fused and isinstance(wb, NF4Weight) and _w4_ok(dy, wb, True):
-                codes, sc = wb.g4w_pack()
-                _count("gemm4w-nf4")
-                dx = native().gemm4w_loradx(dy, codes, sc, wb.shape[1], g_list, a_list, masks, ps)
-            else:
-                c = native().lora_dxc(g_list, a_list, masks, ps)
-                dx = _base_gemm_t(dy, wb, None, None, c)
-                del c
-    ctx.wdq = None
-    dres = dy if ctx.has_residual else None
-    dw = (dy.t() @ x).to(weight.dtype) if (dense and weight is not None and ctx.needs_input_grad[2]) else None
-    dbias = dy.sum(0) if ctx.needs_input_grad[3] else None
-    return (dx, dres, dw, dbias, None, *grads_ab)
+            c = (native().lora_dx2(g_list[0], g_list[1], a_list[0], a_list[1], ctx.masks, ps[0], ps[1]) if ctx.pair
+                 else native().lora_dxc(g_list, a_list, ctx.masks, ps))
+            dx = _base_gemm_t(dy, wb, None, None, c)
+            del c
+    elif need[0]:
+        # adapters without dropout: their g·A as an extra K-slice of the dX GEMM (dropout adapters: lora_acc below)
+        fold = [i for i in range(ctx.nb) if ctx.keys[i] is None]
+        ext_a = ext_b = None
+        if fold:
+            ext_a = _pad_cols(torch.cat([g_list[i].to(dy.dtype) for i in fold], 1))
+            eb = torch.cat([bf16_view(ab[2 * i], dy.dtype) for i in fold], 0)                    # [R, K]
+            ext_b = F.pad(eb, (0, 0, 0, ext_a.shape[1] - eb.shape[0])).t().contiguous()          # [K, Rp]
+        dx = _base_gemm_t(dy, wb, ext_a, ext_b)
+    if dA_done:
+        return dx
+    if keep:
+        _acc_jobs(ctx, _dA_jobs(ctx, x, g_list), grads_ab)
+        return dx
+    for i, br in enumerate(branches):
+        key = ctx.keys[i]
+        if ctx.fast:   # dA += gᵀ·D(x) and (dropout branches) dx += D(g·A), one pass over x / dx
+            upd = dx if (dx is not None and key is not None) else None
+            if need[5 + 2 * i] or upd is not None:
+                out, fresh = _grad_dest(ab[2 * i], dy.device)
+                native().lora_acc(g_list[i], x, 0, x.shape[1], out, False, upd,
+                                  bf16_view(ab[2 * i], dy.dtype) if upd is not None else None,
+                                  br.dropout if key is not None else 0.0, key or 0, det)
+                if need[5 + 2 * i]:
+                    _grad_done(ctx, grads_ab, 2 * i, out, fresh)
+        elif dx is not None and key is not None:   # LoRA input grad through the regenerated dropout mask
+            native().dropout_bwd_add(dx, g_list[i] @ bf16_view(ab[2 * i], dy.dtype), br.dropout, key)
+    return dx
 
 
 def _reference(x, base, bias, branches, residual, training):

@@ -644,7 +644,7 @@ def test_lora_fused_kernels(native_ext, M, K, r, p):
 def test_lora_two_branch_kernels(native_ext, M, K, p0, p1):
     """lora_proj2 (q_proj + v_proj over one x pass, keep bits stored) vs fp32 with each branch's own
     regenerated dropout mask; the backward's per-branch lora_acc (dA and the masked dx term, mask regenerated from
-    the key) and the stored-keep-bit forms (lora_dx2, lora_dA_pair) agree with it."""
+    the key) and the stored-keep-bit forms (lora_dx2, a 2-job dA lora_acc_jobs) agree with it."""
     torch.manual_seed(1)
     x = torch.randn(M, K, device=DEV).to(torch.bfloat16)
     a0 = (0.05 * torch.randn(8, K, device=DEV)).to(torch.bfloat16)
@@ -682,7 +682,7 @@ def test_lora_two_branch_kernels(native_ext, M, K, p0, p1):
     c = native_ext.lora_dx2(g0, g1, a0, a1, masks, p0, p1)
     assert rel_err(c, want - dx0) < 1e-2
     da0c, da1c = torch.zeros(8, K, device=DEV), torch.zeros(8, K, device=DEV)
-    native_ext.lora_dA_pair(g0, g1, x, da0c, da1c, masks, p0, p1)
+    native_ext.lora_acc_jobs([g0, g1], [x, x], [0, 0], [K, K], [da0c, da1c], [False, False], masks, [0, 1], [p0, p1])
     assert rel_err(da0c, g0.t() @ xd0.float()) < 1e-2 and rel_err(da1c, g1.t() @ xd1.float()) < 1e-2
     # dx = dy·W + c in one hipBLASLt call
     dyw = torch.randn(M, 1024, device=DEV).to(torch.bfloat16)
@@ -1007,20 +1007,23 @@ def test_lt_dx_split(native_ext, split):
 
 @pytest.mark.parametrize("M", [2048, 300])
 def test_lora_backward_pair_kernels(native_ext, M):
-    """lora_proj_pair (s_i·dy_i·B_i for two column blocks of dy) and lora_acc_pair (dB_i += dy_iᵀ·xa_i)
-    vs fp32."""
+    """The q+v pair's backward launches: lora_proj_cols (s_i·dy_i·B_i for two column blocks of dy) and a 2-job
+    lora_acc_jobs (dB_i += dy_iᵀ·xa_i) vs fp32; each g bit-equal to the per-adapter lora_proj (the same
+    lora_proj_body<16, 8>, no atomics)."""
     torch.manual_seed(4)
     N, r = 6144, 8
     dy = torch.randn(M, N, device=DEV).to(torch.bfloat16)
     specs = [(0, 4096, 2.0), (5120, 1024, 0.5)]
     bts = [(0.05 * torch.randn(r, n, device=DEV)).to(torch.bfloat16) for _, n, _ in specs]
-    ga, gb = native_ext.lora_proj_pair(dy, specs[0][0], bts[0], specs[0][2], specs[1][0], bts[1], specs[1][2])
+    ga, gb = native_ext.lora_proj_cols(dy, [c0 for c0, _, _ in specs], bts, [s for _, _, s in specs])
     for g, (c0, n, s), bt in zip((ga, gb), specs, bts):
         assert rel_err(g, s * dy[:, c0:c0 + n].float() @ bt.float().t()) < 1e-2
+        assert torch.equal(g, native_ext.lora_proj(dy, c0, n, bt, None, True, 0.0, 0, s))
     xa2 = torch.randn(M, 16, device=DEV)
     xs = [xa2[:, :8], xa2[:, 8:]]
     outs = [torch.full((n, r), 0.25, device=DEV) for _, n, _ in specs]
-    native_ext.lora_acc_pair(xs[0], xs[1], dy, specs[0][0], outs[0], specs[1][0], outs[1])
+    native_ext.lora_acc_jobs(xs, [dy, dy], [c0 for c0, _, _ in specs], [n for _, n, _ in specs], outs, [True, True],
+                             None, [-1, -1], [0.0, 0.0])
     for o, (c0, n, _), xa in zip(outs, specs, xs):
         assert rel_err(o - 0.25, dy[:, c0:c0 + n].float().t() @ xa) < 1e-2
 

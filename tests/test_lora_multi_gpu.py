@@ -83,6 +83,30 @@ def test_lora_proj_cols_and_acc_jobs_match_fp32(native_ext, M):
         assert ((dA[b] - ref_a).norm() / ref_a.norm()) < 1e-2, ("dA", b)
 
 
+def test_lora_acc_jobs_job_boundaries(native_ext):
+    """Four jobs whose k-block ranges are 1, 4, 1 and 1 blocks wide (the first job exactly one block: the job
+    lookup is hit at every boundary), M = 300 with a partial last 128-row block, per-job ranks, two dA jobs over
+    K = 128 with their own keep-bit planes; every output accumulates onto 0.25."""
+    g = torch.Generator(device="cuda").manual_seed(5)
+    M, K = 300, 128
+    ncols, c0s, rb = [128, 512], [0, 256], [8, 16]
+    dy = torch.randn(M, 768, device="cuda", generator=g).bfloat16()
+    x = torch.randn(M, K, device="cuda", generator=g).bfloat16()
+    xa = [torch.randn(M, r, device="cuda", generator=g) for r in rb]
+    gl = [torch.randn(M, r, device="cuda", generator=g) for r in rb]
+    ps = [0.1, 0.3]
+    masks = torch.randint(0, 256, (2, M, K // 8), dtype=torch.uint8, device="cuda", generator=g)
+    dB = [torch.full((n, r), 0.25, device="cuda") for n, r in zip(ncols, rb)]
+    dA = [torch.full((r, K), 0.25, device="cuda") for r in rb]
+    native_ext.lora_acc_jobs(xa + gl, [dy, dy, x, x], c0s + [0, 0], ncols + [K, K], dB + dA,
+                             [True, True, False, False], masks, [-1, -1, 0, 1], [0.0, 0.0] + ps)
+    for b in range(2):
+        ref_b = dy[:, c0s[b]:c0s[b] + ncols[b]].float().t() @ xa[b]
+        assert ((dB[b] - 0.25 - ref_b).norm() / ref_b.norm()) < 1e-2, ("dB", b)
+        ref_a = gl[b].t() @ (x.float() * _unpack(masks[b], K) / (1 - ps[b]))
+        assert ((dA[b] - 0.25 - ref_a).norm() / ref_a.norm()) < 1e-2, ("dA", b)
+
+
 @pytest.mark.parametrize("M,K,nbr", [(512, 1024, 3), (200, 512, 1), (2048, 4096, 4)])
 def test_lora_dxc_matches_fp32(native_ext, M, K, nbr):
     g = torch.Generator(device="cuda").manual_seed(2)

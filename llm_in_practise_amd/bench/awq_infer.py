@@ -152,6 +152,7 @@ def main(argv=None):
     ap.add_argument("--serve-requests", type=int, default=0)
     ap.add_argument("--serve-tokens", type=int, default=256)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fp8", action="store_true", help="also measure an FP8 W8A8 copy of the model (quant/fp8.py)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     from ..quant.eval import self_ppl
@@ -174,6 +175,25 @@ def main(argv=None):
                                        if n.startswith("model.layers") and p.dim() == 2)}
     ref_logp = _next_token_logp(lm, eval_ids)
     lm.invalidate_fusion()
+
+    if a.fp8:
+        import copy
+
+        from ..quant.fp8 import Fp8Linear, quantize_model_fp8
+        lm8 = quantize_model_fp8(copy.deepcopy(lm))
+        lm8.fuse_projections()
+        logp = _next_token_logp(lm8, eval_ids)
+        res["fp8"] = {"decode": _decode_steps(lm8, a.batches, a.ctx, a.steps, a.max_len),
+                      "prefill": _prefill(lm8, *a.prefill, a.steps // 2 or 1),
+                      "self_ppl": self_ppl(lm8, prompts, a.ppl_new),
+                      "weight_bytes": sum(m.fp8.nbytes() for m in lm8.modules() if isinstance(m, Fp8Linear)),
+                      "kl_vs_bf16": (ref_logp.exp() * (ref_logp - logp)).sum(-1).mean().item(),
+                      "top1_agree_vs_bf16": (ref_logp.argmax(-1) == logp.argmax(-1)).float().mean().item()}
+        res["fp8"]["self_ppl_ratio_vs_bf16"] = res["fp8"]["self_ppl"] / res["bf16"]["self_ppl"]
+        res["fp8_decode_speedup"] = {str(b["batch"]): round(b["step_ms"] / q["step_ms"], 3)
+                                     for b, q in zip(res["bf16"]["decode"], res["fp8"]["decode"])}
+        del lm8
+        torch.cuda.empty_cache() if torch.cuda.is_available() else None
 
     t0 = time.perf_counter()
     if a.method == "awq":
@@ -203,7 +223,7 @@ def main(argv=None):
                              for b, q in zip(res["bf16"]["decode"], res["int4"]["decode"])}
     if a.serve_requests:
         res["int4"]["serve"] = _serve(lm, a.serve_requests, a.serve_tokens, max(a.batches))
-    for k in ("bf16", "int4"):
+    for k in [k for k in ("bf16", "fp8", "int4") if k in res]:
         if not math.isfinite(res[k]["self_ppl"]):
             res[k]["self_ppl"] = None
     line = json.dumps(res)

@@ -275,11 +275,16 @@ def _parallel(a=None):
 def _load_for_inference(path, adapter=None, device=None, quant=None, fuse=True, tp_group=None, pp_group=None):
     from ..models.qwen3 import BitsAndBytesConfig, Qwen3ForCausalLM, qwen3_config
     dev = device or _device()
+    if quant == "fp8" and (tp_group is not None or pp_group is not None):
+        raise SystemExit(_FP8_NO_TP)
     if tp_group is not None or pp_group is not None:   # shard the bf16 weights (+ adapter), THEN quantise
         from ..parallel.pipeline_parallel import apply_pipeline_parallel
         from ..parallel.tensor_parallel import apply_tensor_parallel
         from ..peft.lora import quantize_model_nf4
         m = _load_for_inference(path, adapter, dev, None, fuse=False)
+        from ..quant.fp8 import Fp8Linear
+        if any(isinstance(mod, Fp8Linear) for mod in m.modules()):      # an FP8 checkpoint, whatever flag named it
+            raise SystemExit(_FP8_NO_TP)
         if pp_group is not None:
             apply_pipeline_parallel(m, pp_group)
         if tp_group is not None:
@@ -303,6 +308,12 @@ def _load_for_inference(path, adapter=None, device=None, quant=None, fuse=True, 
         else:
             bnb = BitsAndBytesConfig(load_in_4bit=True) if quant == "nf4" else None
             m = Qwen3ForCausalLM.from_pretrained(path, dtype=torch.bfloat16, device=dev, quantization_config=bnb)
+    if quant == "fp8":                  # data-free W8A8 after the bf16 load (an FP8 checkpoint already holds its codes)
+        from ..quant.fp8 import Fp8Linear, quantize_model_fp8
+        if not any(isinstance(mod, Fp8Linear) for mod in m.modules()):
+            quantize_model_fp8(m)
+        if not any(isinstance(mod, Fp8Linear) for mod in m.modules()):
+            raise SystemExit(f"fp8: {path} has no bf16 linear layers to quantise (already quantised another way?)")
     if adapter:
         from ..peft.lora import PeftModel
         m = PeftModel.from_pretrained(m, adapter)
@@ -401,6 +412,14 @@ def cmd_quantize(a):  # calibration hooks need the unfused Linear modules
             tok = load_tokenizer(a.tokenizer or a.model)
         except Exception:
             tok = None
+    if a.method == "fp8":                # data-free: no calibration set
+        from ..quant.fp8 import quantize_model_fp8
+        if a.format != "compressed-tensors":
+            raise SystemExit("--method fp8 writes --format compressed-tensors only")
+        quantize_model_fp8(m)
+        save_quantized(m, a.out, a.format, tok)
+        print(json.dumps({"quantized": a.out, "method": a.method, "format": a.format}))
+        return
     calib = _calib_ids(a, tok, m.config.vocab_size, dev)
     if a.method == "gptq":
         gptq_quantize_model(m, calib, a.group_size, a.sym)
@@ -443,6 +462,8 @@ def cmd_eval_quant(a):
     print(json.dumps({"self_ppl": ppl, "pass": ppl < PASS_THRESHOLD, "threshold": PASS_THRESHOLD}))
 
 
+_FP8_NO_TP = ("--quantization fp8 runs on one GPU: tensor / pipeline parallel sizes above 1 are not supported "
+              "(the per-channel scales are not sharded)")
 _VLLM_QUANT = {"awq": ("awq", "compressed-tensors"), "awq_marlin": ("awq", "compressed-tensors"),
                "gptq": ("gptq", "compressed-tensors"), "gptq_marlin": ("gptq", "compressed-tensors"),
                "compressed-tensors": ("compressed-tensors", "awq", "gptq")}
@@ -479,9 +500,19 @@ def _vllm_compat(a):
     elif dt == "float32":
         raise SystemExit("--dtype float32: not supported (bf16 kernels)")
     vq = getattr(a, "vllm_quant", None)
+    if vq == "fp8":
+        a.quant = "fp8"
+    cfgp = os.path.join(a.model, "config.json")
+    if getattr(a, "quant", None) != "fp8" and os.path.exists(cfgp):     # a stored FP8 checkpoint, whatever flag names it
+        from ..quant.io import is_fp8_config
+        with open(cfgp) as f:
+            if is_fp8_config(json.load(f).get("quantization_config")):
+                a.quant = "fp8"
+    if getattr(a, "quant", None) == "fp8" and max(int(getattr(a, "tp", None) or 1), int(getattr(a, "pp", None) or 1)) > 1:
+        raise SystemExit(_FP8_NO_TP)
     if vq == "bitsandbytes":
         a.quant = "nf4"
-    elif vq is not None:
+    elif vq is not None and vq != "fp8":
         cfgp = os.path.join(a.model, "config.json")
         qc = None
         if os.path.exists(cfgp):
@@ -1001,7 +1032,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.set_defaults(fn=cmd_merge)
 
     p = sub.add_parser("quantize")
-    p.add_argument("--method", default="awq", choices=["awq", "gptq", "rtn"])
+    p.add_argument("--method", default="awq", choices=["awq", "gptq", "rtn", "fp8"])
     p.add_argument("--model", required=True, help="HF dir or random:<qwen3 preset>")
     p.add_argument("--out", required=True)
     p.add_argument("--format", default="compressed-tensors", choices=["compressed-tensors", "gptq", "awq"])
@@ -1032,10 +1063,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--model", default=None)
     p.add_argument("--adapter")
     p.add_argument("--tokenizer")
-    p.add_argument("--quant", choices=["nf4"])
+    p.add_argument("--quant", choices=["nf4", "fp8"])
     p.add_argument("--quantization", dest="vllm_quant", default=None,
-                   choices=["awq", "awq_marlin", "gptq", "gptq_marlin", "compressed-tensors", "bitsandbytes"],
-                   help="vLLM flag: int4 checkpoints load by their quantization_config; bitsandbytes = NF4")
+                   choices=["awq", "awq_marlin", "gptq", "gptq_marlin", "compressed-tensors", "bitsandbytes", "fp8"],
+                   help="vLLM flag: int4 / FP8 checkpoints load by their quantization_config; bitsandbytes = NF4; "
+                        "fp8 = dynamic W8A8 (e4m3) quantised after a bf16 load")
     p.add_argument("--dtype", default="auto", choices=["auto", "bfloat16", "bf16", "half", "float16", "float32"])
     p.add_argument("--gpu-memory-utilization", dest="gpu_memory_utilization", type=float, default=None,
                    help="vLLM flag: fraction of device memory for weights + KV; sizes the KV slot pool")

@@ -142,6 +142,15 @@ void launch_embedding_bwd(const void*, int, const int64_t*, float*, int64_t, int
 void launch_dropout_bwd_add(void*, const void*, size_t, uint64_t, float, hipStream_t);
 int pool_embed_split_rows();
 void launch_pool_embed(const void*, int, long, const int*, float*, float*, int*, int, int, int, int, int, hipStream_t);
+void launch_fp8_quant_rows(const void*, long, void*, float*, int, int, bool, hipStream_t);
+bool fp8_quant_supported(int);
+bool fp8_gemm_supported(int, int);
+int fp8_skinny_max_m();
+int fp8_skinny_splits(int, int);
+void launch_fp8_skinny(const void*, const void*, const float*, const float*, const void*, const void*, void*, float*,
+                       int, int, int, hipStream_t);
+void launch_fp8_tiled(const void*, const void*, const float*, const float*, const void*, const void*, void*, int, int,
+                      int, int, hipStream_t);
 
 namespace {
 
@@ -1244,6 +1253,81 @@ Tensor pool_embed(Tensor hidden, Tensor cu_seqlens, int64_t mode, int64_t dims, 
   return out;
 }
 
+// ------------------------------------------------------------------ FP8 W8A8 linears (csrc/kernels/fp8.hip)
+// x [R, K] bf16 (unit inner stride, 16-B aligned rows) -> (e4m3 codes [R, K], fp32 scale [R]); with swiglu x is
+// [R, 2K] = [g | u] and the rows quantised are bf16(silu(g)·u).
+std::vector<Tensor> fp8_quant_rows_impl(Tensor x, bool swiglu, const char* who) {
+  CHECK_CUDA(x); CHECK_BF16(x);
+  TORCH_CHECK(x.dim() == 2 && x.size(0) > 0 && x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              who, ": x must be [R, K] bf16 with unit inner stride and 16-byte aligned rows");
+  TORCH_CHECK(!swiglu || x.size(1) % 2 == 0, who, ": gu must be [R, 2F]");
+  const int64_t R = x.size(0), K = swiglu ? x.size(1) / 2 : x.size(1);
+  TORCH_CHECK(x.stride(0) >= x.size(1) && fp8_quant_supported((int)K), who, ": K % 16 == 0 and K <= 16384, got ", K);
+  TORCH_CHECK(R <= 0x7fffffff, who, ": too many rows");
+  Tensor codes = at::empty({R, K}, x.options().dtype(at::kFloat8_e4m3fn));
+  Tensor scale = at::empty({R}, x.options().dtype(at::kFloat));
+  launch_fp8_quant_rows(x.data_ptr(), (long)x.stride(0), codes.data_ptr(), scale.data_ptr<float>(), (int)R, (int)K,
+                        swiglu, stream());
+  return {codes, scale};
+}
+std::vector<Tensor> fp8_quant_rows(Tensor x) { return fp8_quant_rows_impl(x, false, "fp8_quant_rows"); }
+std::vector<Tensor> fp8_swiglu_quant_rows(Tensor gu) { return fp8_quant_rows_impl(gu, true, "fp8_swiglu_quant_rows"); }
+
+// xq [M, K] / wq [N, K] e4m3 codes, sx [M] / sw [N] fp32, bias [N] bf16, residual [M, N] bf16 -> bf16 [M, N].
+// skinny: M <= 32 (weight-streaming, fixed-order split-K); tiled: any M (wt = 2 / 4 forces the 64 / 128 tile).
+Tensor fp8_gemm(Tensor xq, Tensor sx, Tensor wq, Tensor sw, optional<Tensor> bias, optional<Tensor> residual,
+                bool skinny, int64_t wt) {
+  auto is8 = [](const Tensor& t) { return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kByte; };
+  CHECK_CUDA(xq); CHECK_CUDA(wq); CHECK_CONTIG(xq); CHECK_CONTIG(wq); CHECK_CONTIG(sx); CHECK_CONTIG(sw);
+  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && is8(xq) && is8(wq) && xq.size(1) == wq.size(1),
+              "fp8_gemm: codes must be e4m3 [M, K] and [N, K]");
+  const int64_t M = xq.size(0), K = xq.size(1), N = wq.size(0);
+  TORCH_CHECK(M >= 1 && M <= 0x7fffffff && fp8_gemm_supported((int)N, (int)K), "fp8_gemm: M >= 1, N % 16, K % 128");
+  TORCH_CHECK(!skinny || M <= fp8_skinny_max_m(), "fp8_gemm_skinny: M <= ", fp8_skinny_max_m());
+  TORCH_CHECK(wt == 0 || wt == 2 || wt == 4, "fp8_gemm_tiled: wt 0 (auto), 2 or 4");
+  TORCH_CHECK(sx.is_cuda() && sw.is_cuda() && sx.scalar_type() == at::kFloat && sw.scalar_type() == at::kFloat &&
+                  sx.numel() == M && sw.numel() == N,
+              "fp8_gemm: scales fp32 [M] and [N]");
+  auto al = [](const Tensor& t, uintptr_t a) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0; };
+  TORCH_CHECK(al(xq, 16) && al(wq, 16) && al(sw, 16), "fp8_gemm: 16-byte aligned operands");
+  const void *bp = nullptr, *rp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    CHECK_CUDA((*bias)); CHECK_BF16((*bias)); CHECK_CONTIG((*bias));
+    TORCH_CHECK(bias->numel() == N && al(*bias, 8), "fp8_gemm: bias bf16 [N], 8-byte aligned");
+    bp = bias->data_ptr();
+  }
+  if (residual.has_value() && residual->defined()) {
+    CHECK_CUDA((*residual)); CHECK_BF16((*residual)); CHECK_CONTIG((*residual));
+    TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == N && al(*residual, 8),
+                "fp8_gemm: residual bf16 [M, N]");
+    rp = residual->data_ptr();
+  }
+  Tensor out = at::empty({M, N}, xq.options().dtype(at::kBFloat16));
+  if (skinny) {
+    const int ks = fp8_skinny_splits((int)N, (int)K);
+    Tensor part;
+    if (ks > 1) part = at::empty({ks, M, N}, sx.options());
+    launch_fp8_skinny(xq.data_ptr(), wq.data_ptr(), sx.data_ptr<float>(), sw.data_ptr<float>(), bp, rp, out.data_ptr(),
+                      ks > 1 ? part.data_ptr<float>() : nullptr, (int)M, (int)N, (int)K, stream());
+  } else {
+    launch_fp8_tiled(xq.data_ptr(), wq.data_ptr(), sx.data_ptr<float>(), sw.data_ptr<float>(), bp, rp, out.data_ptr(),
+                     (int)M, (int)N, (int)K, (int)wt, stream());
+  }
+  return out;
+}
+Tensor fp8_gemm_skinny(Tensor xq, Tensor sx, Tensor wq, Tensor sw, optional<Tensor> bias, optional<Tensor> residual) {
+  return fp8_gemm(xq, sx, wq, sw, bias, residual, true, 0);
+}
+Tensor fp8_gemm_tiled(Tensor xq, Tensor sx, Tensor wq, Tensor sw, optional<Tensor> bias, optional<Tensor> residual,
+                      int64_t wt) {
+  return fp8_gemm(xq, sx, wq, sw, bias, residual, false, wt);
+}
+int64_t fp8_skinny_splits_py(int64_t N, int64_t K) {
+  TORCH_CHECK(fp8_gemm_supported((int)N, (int)K), "fp8_skinny_splits: N % 16, K % 128");
+  return fp8_skinny_splits((int)N, (int)K);
+}
+
 // ------------------------------------------------------------------ fused LoRA branch kernels
 // out = scale·D(x)·Wᵀ over x[:, c0:c0+K] (row stride = x.stride(0)); writes bf16 into outb (a column
 // slice view, any row stride) and/or returns fp32 [M, r].
@@ -1982,6 +2066,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w4mm", &w4mm, py::arg("x"), py::arg("codes"), py::arg("sc2"), py::arg("N"), py::arg("gs"),
         py::arg("residual") = py::none(), py::arg("nkb") = 0);
   m.def("w4mm_ok", &w4mm_ok);
+  m.def("fp8_quant_rows", &fp8_quant_rows);
+  m.def("fp8_swiglu_quant_rows", &fp8_swiglu_quant_rows);
+  m.def("fp8_gemm_skinny", &fp8_gemm_skinny, py::arg("xq"), py::arg("sx"), py::arg("wq"), py::arg("sw"),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none());
+  m.def("fp8_gemm_tiled", &fp8_gemm_tiled, py::arg("xq"), py::arg("sx"), py::arg("wq"), py::arg("sw"),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(), py::arg("wt") = 0);
+  m.def("fp8_skinny_splits", &fp8_skinny_splits_py);
   m.def("w4g", &w4g, py::arg("x"), py::arg("codes"), py::arg("sc2"), py::arg("N"), py::arg("gs"),
         py::arg("residual") = py::none(), py::arg("ks") = 0);
   m.def("w4g_ok", &w4g_ok);

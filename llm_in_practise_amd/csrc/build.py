@@ -32,6 +32,12 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX")
 
 
+# Per-source hipcc flags.  fp8.hip is built with the packed fp32 VALU forms (v_pk_{add,mul,fma}_f32) off: a policy
+# for kernels added from this file on, so that their fp32 epilogues and fixed-order sums compile to the scalar
+# instructions the source spells out.  Per lane the result is the same IEEE operation.
+_EXTRA_KFLAGS = {"fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _torch_flags():
     from torch.utils import cpp_extension as ce
     inc = ce.include_paths(device_type="cuda") if "device_type" in ce.include_paths.__code__.co_varnames else ce.include_paths(True)
@@ -98,7 +104,8 @@ def build_hip_extension(jobs: int | None = None, verbose: bool = True) -> str:
     srcs = sorted(glob.glob(os.path.join(kdir, "*.hip")))
     jobs = jobs or int(os.environ.get("MAX_JOBS", "8"))
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
-        futs = [ex.submit(_compile, s, kflags, [hipcc], headers) for s in srcs]
+        futs = [ex.submit(_compile, s, kflags + _EXTRA_KFLAGS.get(os.path.basename(s), []), [hipcc], headers)
+                for s in srcs]
         bsrc = os.path.join(HERE, "bindings.cpp")   # shares structs with the kernels through their headers
         futs.append(ex.submit(_compile, bsrc, bflags, ["g++"], _local_includes(bsrc)))
         objs = [f.result() for f in futs]

@@ -9,6 +9,7 @@ import torch.nn as nn
 from ..ops.attention import flash_attention_varlen, native_ok
 from ..ops.linear import LoraBranch, fused_linear
 from ..peft.lora import Linear4bit, LoraLayer, base_of
+from ..quant.fp8 import Fp8Linear, Fp8Weight, fp8_linear
 from ..quant.int4 import Int4Linear, Int4Weight, int4_linear
 from ..quant.nf4 import NF4Weight, concat_nf4
 
@@ -82,6 +83,16 @@ class FusedProjection:
                                   l.group_size, l.sym))
                 r0 += n
             biases = [l.bias for l in leaves]
+        elif all(isinstance(l, Fp8Linear) for l in leaves):    # W8A8: codes and per-channel scales concat along N
+            codes = torch.cat([l.codes for l in leaves], 0)
+            scale = torch.cat([l.scale for l in leaves], 0)
+            self.base = Fp8Weight(codes, scale, (codes.shape[0], leaves[0].in_features))
+            r0 = 0
+            for l in leaves:
+                n = l.out_features
+                l.load(Fp8Weight(codes[r0:r0 + n], scale[r0:r0 + n], (n, l.in_features)))
+                r0 += n
+            biases = [l.bias for l in leaves]
         else:
             w = torch.cat([l.weight.detach() for l in leaves], 0)
             self.base = w
@@ -116,8 +127,9 @@ class FusedProjection:
         return out
 
     def __call__(self, x, residual=None, training: bool = True):
-        if isinstance(self.base, Int4Weight):
-            y = int4_linear(x, self.base, self.bias, residual)
+        if isinstance(self.base, (Int4Weight, Fp8Weight)):
+            lin = int4_linear if isinstance(self.base, Int4Weight) else fp8_linear
+            y = lin(x, self.base, self.bias, residual)
             for br in self.branches(False):       # inference-only base: unmerged adapters as plain low-rank adds
                 y2 = y.view(-1, y.shape[-1])
                 y2[:, br.c0:br.c1] += ((x.reshape(-1, x.shape[-1]) @ br.a.t().to(x.dtype)) @ br.b.t().to(x.dtype)) * br.scaling
@@ -151,6 +163,9 @@ def project(mods: list[nn.Module], x: torch.Tensor, residual: torch.Tensor | Non
         if isinstance(m, Int4Linear):            # o_proj / down_proj of a W4A16 model: residual in the epilogue
             y = int4_linear(x.to(torch.bfloat16) if x.is_cuda else x, m.int4, m.bias, residual)
             return _apply_multi_lora(mods, [m.out_features], x, y)
+        if isinstance(m, Fp8Linear):             # o_proj / down_proj of a W8A8 model; x may be quantised rows
+            y = fp8_linear(x, m.fp8, m.bias, residual)
+            return y if isinstance(x, tuple) else _apply_multi_lora(mods, [m.out_features], x, y)
         if _trainable_base(m) or not isinstance(_leaf_linear(m), (nn.Linear, Linear4bit)):
             y = m(x)
             y = _apply_multi_lora(mods, [y.shape[-1]], x, y)
@@ -176,6 +191,8 @@ def can_fuse(mods: list[nn.Module]) -> bool:
         return all(l.in_features == k and (l.out_features * l.in_features // l.blocksize) % 256 == 0 for l in leaves)
     if all(isinstance(l, Int4Linear) for l in leaves):
         return len({(l.in_features, l.group_size, l.sym) for l in leaves}) == 1
+    if all(isinstance(l, Fp8Linear) for l in leaves):
+        return len({l.in_features for l in leaves}) == 1
     if all(isinstance(l, nn.Linear) for l in leaves):
         return len({l.in_features for l in leaves}) == 1 and len({l.weight.dtype for l in leaves}) == 1
     return False

@@ -35,6 +35,7 @@ from ..ops.norm import RMSNorm, rms_norm, rms_norm_residual
 from ..ops.rope import apply_rope, qk_norm_rope
 from ..parallel.tensor_parallel import tp_all_reduce
 from ..peft.lora import LoraLayer, base_of
+from ..quant.fp8 import Fp8Linear, swiglu_quantize_rows
 from ..quant.int4 import Int4Linear
 from ..ops.embedding import Embedding
 from .common import CausalLMOutput, FusedProjection, KVCache, PackedPrefill, _leaf_linear, can_fuse, project
@@ -251,8 +252,8 @@ class Qwen3MLP(nn.Module):
         if any((isinstance(m, LoraLayer) and not m.merged) or getattr(_leaf_linear(m), "_mlora", None) is not None
                for m in mods):
             return None
-        if isinstance(_leaf_linear(self.down_proj), Int4Linear):
-            return None     # W4A16 runs as separate projections (base_of would dequantise the weight)
+        if isinstance(_leaf_linear(self.down_proj), (Int4Linear, Fp8Linear)):
+            return None     # W4A16 / W8A8 run as separate projections (base_of would dequantise the weight)
         down_base, down_bias = base_of(self.down_proj)
         if self._gu.bias is not None or down_bias is not None:
             return None
@@ -267,6 +268,9 @@ class Qwen3MLP(nn.Module):
         if bases is not None:
             return swiglu_mlp(x, bases[0], bases[1], residual)
         gu = project([self.gate_proj, self.up_proj], x, None, tr, self._gu)
+        if isinstance(self.down_proj, Fp8Linear) and getattr(self.down_proj, "_mlora", None) is None:
+            # W8A8: SwiGLU and the down GEMM's row quantiser in one launch, no bf16 h round trip
+            return project([self.down_proj], swiglu_quantize_rows(gu), residual, tr)
         if self.tp_group is None:
             return project([self.down_proj], swiglu_fused(gu), residual, tr)
         y = project([self.down_proj], swiglu_fused(gu), residual if self.tp_rank == 0 else None, tr)

@@ -2,11 +2,17 @@
 // stream (so every op is capturable in a hipGraph and ordered with PyTorch's own work).
 #include "kernels/lora_epi.h"
 #include "kernels/sample_rows.h"
+#include "nf4_resident.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
+#include <memory>
+#include <mutex>
+#include <tuple>
 #include <vector>
 
 // ---- launcher declarations (csrc/kernels/*.hip)
@@ -774,6 +780,104 @@ Tensor nf4_dequant_fast(Tensor codes, Tensor absmax, int64_t N, int64_t K) {
   auto w = at::empty({N, K}, codes.options().dtype(at::kBFloat16));
   launch_nf4_dequant2(codes.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.data_ptr(), N * K, stream());
   return w;
+}
+
+// ---- resident expansions (nf4_resident.h: the registry's rules).  A frozen base's codes and scales are the same
+// bytes in every step, so its bf16 expansion is written once and handed out again: a hit launches nothing.
+struct Nf4Resident {
+  Tensor codes, scales, w;          // the references that keep the key's pointers from being recycled
+  std::shared_ptr<void> ready;      // hipEvent_t recorded behind the expansion kernel
+  hipStream_t producer = nullptr;
+  std::vector<hipStream_t> ordered; // other streams that already wait on ``ready``
+};
+
+struct Nf4ResidentState {
+  std::mutex mu;
+  std::map<int, Nf4ResidentRegistry<Nf4Resident>> by_device;
+};
+
+// (never destroyed: tensors released during static destruction would outlive the HIP runtime)
+Nf4ResidentState& nf4_resident_state() {
+  static Nf4ResidentState* s = new Nf4ResidentState();
+  return *s;
+}
+
+uint64_t tensor_version(const Tensor& t) { return t.unsafeGetTensorImpl()->version_counter().current_version(); }
+
+// (w, launched): the bf16 expansion of a frozen NF4 base, kept for the process under ``budget_bytes`` per device
+// (<= 0: nf4_dequant_fast).  ``launched`` is false on a hit.  Over budget, or while the stream is being captured
+// into a graph (a captured kernel writes nothing now), the result is a throw-away copy.
+std::tuple<Tensor, bool> nf4_dequant_resident(Tensor codes, Tensor absmax, int64_t N, int64_t K, int64_t budget_bytes) {
+  CHECK_CUDA(codes);
+  CHECK_CUDA(absmax);
+  const hipStream_t cur = stream();
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(cur, &cap) == hipSuccess, "nf4_dequant_resident: hipStreamIsCapturing");
+  if (budget_bytes <= 0 || cap != hipStreamCaptureStatusNone) return {nf4_dequant_fast(codes, absmax, N, K), true};
+  Nf4ResidentKey key;
+  key.codes = reinterpret_cast<uintptr_t>(codes.data_ptr());
+  key.scales = reinterpret_cast<uintptr_t>(absmax.data_ptr());
+  key.n = N;
+  key.k = K;
+  key.codes_version = tensor_version(codes);
+  key.scales_version = tensor_version(absmax);
+  auto& st = nf4_resident_state();
+  std::lock_guard<std::mutex> lock(st.mu);
+  auto& reg = st.by_device[codes.get_device()];
+  Nf4Resident* e = reg.find(key);
+  // a held tensor re-pointed at other storage (Tensor.set_) no longer guards its old pointer
+  if (e && (reinterpret_cast<uintptr_t>(e->codes.data_ptr()) != key.codes ||
+            reinterpret_cast<uintptr_t>(e->scales.data_ptr()) != key.scales)) {
+    reg.drop(key.codes);
+    e = nullptr;
+  }
+  if (e) {
+    if (cur != e->producer && std::find(e->ordered.begin(), e->ordered.end(), cur) == e->ordered.end()) {
+      TORCH_CHECK(hipStreamWaitEvent(cur, static_cast<hipEvent_t>(e->ready.get()), 0) == hipSuccess,
+                  "nf4_dequant_resident: hipStreamWaitEvent");
+      e->w.record_stream(c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().unwrap());
+      e->ordered.push_back(cur);
+    }
+    return {e->w, false};
+  }
+  Tensor w = nf4_dequant_fast(codes, absmax, N, K);
+  const int64_t bytes = N * K * 2;
+  if (reg.admits(bytes, budget_bytes)) {
+    hipEvent_t ev = nullptr;
+    TORCH_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess, "nf4_dequant_resident: hipEventCreate");
+    std::shared_ptr<void> ready(ev, [](void* p) { (void)hipEventDestroy(static_cast<hipEvent_t>(p)); });
+    TORCH_CHECK(hipEventRecord(ev, cur) == hipSuccess, "nf4_dequant_resident: hipEventRecord");
+    reg.insert(key, bytes, budget_bytes, Nf4Resident{codes, absmax, w, std::move(ready), cur, {}});
+  }
+  return {w, true};
+}
+
+// Drops the entry of one base (its owner went away); true when there was one.  n, k guard a fused base whose
+// first part shares its codes pointer.
+bool nf4_resident_drop(int64_t codes_ptr, int64_t N, int64_t K) {
+  auto& st = nf4_resident_state();
+  std::lock_guard<std::mutex> lock(st.mu);
+  for (auto& dr : st.by_device) {
+    const Nf4ResidentKey* k = dr.second.key_at(static_cast<uintptr_t>(codes_ptr));
+    if (k && k->n == N && k->k == K) return dr.second.drop(static_cast<uintptr_t>(codes_ptr));
+  }
+  return false;
+}
+
+void nf4_resident_clear() {
+  auto& st = nf4_resident_state();
+  std::lock_guard<std::mutex> lock(st.mu);
+  for (auto& dr : st.by_device) dr.second.clear();
+}
+
+// bytes resident on ``device`` (< 0: on every device of this process)
+int64_t nf4_resident_bytes(int64_t device) {
+  auto& st = nf4_resident_state();
+  std::lock_guard<std::mutex> lock(st.mu);
+  int64_t b = 0;
+  for (auto& dr : st.by_device)
+    if (device < 0 || dr.first == device) b += dr.second.bytes();
+  return b;
 }
 
 // background expansion of up to 4 NF4 weights in one small persistent grid (see gemm.hip)
@@ -2059,6 +2163,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nf4_quantize", &nf4_quantize);
   m.def("nf4_dequant", &nf4_dequant);
   m.def("nf4_dequant_fast", &nf4_dequant_fast);
+  m.def("nf4_dequant_resident", &nf4_dequant_resident);
+  m.def("nf4_resident_drop", &nf4_resident_drop);
+  m.def("nf4_resident_clear", &nf4_resident_clear);
+  m.def("nf4_resident_bytes", &nf4_resident_bytes, pybind11::arg("device") = -1);
   m.def("gemm_skinny", &gemm_skinny);
   m.def("lt_linear", &lt_linear);
   m.def("lt_dx", &lt_dx);

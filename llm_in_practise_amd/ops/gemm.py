@@ -3,8 +3,10 @@
 * Training / prefill sizes (M >= 256): the hand-written MFMA GEMM ``gemm4w`` (csrc/kernels/gemm4w*.hip) —
   forward with the residual in its epilogue, backward dX reading W as stored (transposed-B), split-K by its
   own cost model.  An NF4 base (QLoRA) either feeds its 4-bit codes straight into gemm4w (the NF4
-  dequant-GEMM: the codes expanded to bf16 between the load and the LDS B image) or is expanded once per
-  step at HBM speed (``nf4_dequant3_k``) when that copy serves two GEMMs (forward + dX): ``_nf4_w4``.
+  dequant-GEMM: the codes expanded to bf16 between the load and the LDS B image) or is expanded at HBM
+  speed (``nf4_dequant3_k``) when that copy serves two GEMMs (forward + dX): ``_nf4_w4``.  In ``auto`` /
+  ``expand`` mode that copy is resident — written once per run, 13.9 GB for Qwen3-8B, peak HBM of the
+  headline step 29.2 GiB as before (``_nf4_expand``); ``w4`` is the lean mode (19.9 GiB, no bf16 weights).
 * Decode sizes: the split-K weight-streaming kernels (``skinny.hip``, ``gemv_w4``).
 * Shapes no kernel takes (CPU tensors, K % 64): torch.
 * ``GEMM_STATS`` counts every GEMM launch by form (bench.py's kernel-provenance record).
@@ -16,10 +18,12 @@ from __future__ import annotations
 
 import collections
 import os
+import weakref
 
 import torch
 
 from ..quant.nf4 import NF4Weight, dequantize_nf4
+from . import _native
 from ._native import native
 
 _MIN_M = 256     # training / prefill-sized GEMMs: gemm4w and the fused LoRA paths
@@ -81,8 +85,8 @@ def _nf4_dequant_bf16(q: NF4Weight) -> torch.Tensor:
 # shapes (profiles/r4/gemm4w_nf4_ab.txt): the in-kernel expansion costs 1.1-1.2x the bf16 gemm4w time
 # (the 3-VALU-per-element table lookup is only partly hidden beside 16x16x32 MFMAs), the same as an
 # expansion + bf16 GEMM when that copy serves ONE GEMM.  "auto" therefore expands where the copy is
-# reused — a training forward whose backward needs dX (the copy is kept for it: ≈14 GB transient for
-# Qwen3-8B), a checkpointed layer (one expansion per optimizer step, below) — and feeds the codes
+# reused — a training forward whose backward needs dX (the copy is kept for it: ≈14 GB for Qwen3-8B,
+# resident for the run, below), a checkpointed layer (forward and recompute) — and feeds the codes
 # straight in everywhere else (inference, no-grad prefill, frozen inputs): no transient bf16 weights.
 # "w4" everywhere is the memory-lean training mode (peak HBM ≈ the 4-bit model + activations).
 _NF4_MODE = os.environ.get("LIPA_NF4_GEMM", "auto")
@@ -96,36 +100,63 @@ def _nf4_w4(reused: bool) -> bool:
     return not (reused or _IN_CKPT[0])
 
 
-# NF4-aware activation checkpointing: inside a checkpointed layer (its forward AND its backward
-# recompute) the bf16 expansion of each frozen NF4 base is made once per optimizer step and reused —
-# the reference-faithful step (gradient checkpointing + sequential GA micro-steps) otherwise expands
-# every weight 2 × GA times per step.  The copies are held in ONE registry, bounded by
-# LIPA_CKPT_NF4_CACHE_GB (default 32; 0 = off: every call expands), and released eagerly when the
-# optimizer steps (``nf4_cache_advance``: optim/adamw.py, parallel/zero.py; an optimizer that never
-# calls it keeps at most the budget).  Memory: the budget is the cost — Qwen3-8B's bases expand to
-# 13.9 GB (peak HBM of the faithful bench step: README §3).
-_CKPT_BUDGET = float(os.environ.get("LIPA_CKPT_NF4_CACHE_GB", "32")) * 2 ** 30
+# Resident expansions: a frozen base's codes and scales are bit-identical in every step of a run, so the
+# bf16 expansion of a module-owned base (``NF4Weight.resident``: the Linear4bit / fused-projection bases
+# of a quantised model) is written ONCE and kept by the native registry (csrc/nf4_resident.h, keyed on the
+# codes pointer, verified by the scales pointer, the shape and both tensors' versions — an in-place rewrite
+# of a base re-expands).  A hit launches nothing: the "expand" form of every later step — the training
+# forward whose backward needs dX, a checkpointed layer's forward and recompute — reads the kept copy.
+# Memory: LIPA_NF4_RESIDENT_GB per device (default 32; 0 = off: every call expands; the older
+# LIPA_CKPT_NF4_CACHE_GB is honoured when the new variable is unset).  Qwen3-8B's bases expand to 13.9 GB,
+# which "auto" already held at the forward / backward turn, so the peak is unchanged and the floor between
+# steps rises (README §3).  Over budget nothing is evicted: the call gets a throw-away copy.  Temporaries
+# (``resident`` off: ZeRO-3's gathered partitions, any NF4Weight made by hand) expand per call as before,
+# and "w4" mode never expands at all.
+def _resident_budget(env=os.environ) -> int:
+    gb = env.get("LIPA_NF4_RESIDENT_GB")
+    if gb is None:
+        gb = env.get("LIPA_CKPT_NF4_CACHE_GB", "32")
+    return int(float(gb) * 2 ** 30)
+
+
+_RESIDENT_BUDGET = _resident_budget()
 _IN_CKPT = [0]
-_CACHE: dict = {}        # id(NF4Weight) -> (weight, bf16 expansion)
-_CACHE_BYTES = [0]
 
 
 def nf4_cache_advance():
-    """Called by the optimizers at every step: the expanded copies of the finished step are released."""
-    _CACHE.clear()
-    _CACHE_BYTES[0] = 0
+    """Kept for the optimizers that call it at every step: expansions are resident for the run now, nothing
+    is released here."""
+
+
+def _drop_resident(ptr: int, n: int, k: int):
+    try:
+        native().nf4_resident_drop(ptr, n, k)
+    except Exception:      # interpreter shutdown: the extension may already be gone
+        pass
+
+
+def nf4_resident_clear():
+    """Return the memory of every resident expansion (``merge_and_unload``, a model being replaced)."""
+    if _native._C is not None:       # (an extension that was never loaded holds nothing)
+        _native._C.nf4_resident_clear()
+
+
+def nf4_resident_bytes() -> int:
+    return int(_native._C.nf4_resident_bytes()) if _native._C is not None else 0
 
 
 def _nf4_expand(q: NF4Weight) -> torch.Tensor:
-    """The bf16 expansion for the "expand" form (cached inside checkpointed layers, see above)."""
-    if _IN_CKPT[0]:
-        hit = _CACHE.get(id(q))
-        if hit is not None and hit[0] is q:
-            return hit[1]
-    w = _nf4_dequant_bf16(q)
-    if _IN_CKPT[0] and _CACHE_BYTES[0] + w.numel() * 2 <= _CKPT_BUDGET:
-        _CACHE[id(q)] = (q, w)
-        _CACHE_BYTES[0] += w.numel() * 2
+    """The bf16 expansion for the "expand" form: the resident copy of a module-owned base, a fresh one else."""
+    if not (q.resident and _RESIDENT_BUDGET > 0 and q.codes.is_cuda):
+        return _nf4_dequant_bf16(q)
+    n, k = q.shape
+    w, launched = native().nf4_dequant_resident(q.codes, q.gemv_scales(), n, k, _RESIDENT_BUDGET)
+    if launched:
+        _count("nf4-expansion")
+        if "_resident_fin" not in q.__dict__:    # the entry goes when its owner does (it holds the codes alive)
+            fin = weakref.finalize(q, _drop_resident, q.codes.data_ptr(), n, k)
+            fin.atexit = False
+            q.__dict__["_resident_fin"] = fin
     return w
 
 
@@ -166,7 +197,7 @@ def _base_gemm(x, base, ext_a=None, ext_b=None, residual=None):
         if _w4_ok(x, base, False):                  # the NF4 dequant-GEMM (gemm4w reads the codes)
             y = _w4_gemm(x, base, False, None if residual is None else residual.contiguous())
             return y if ext_a is None else y.addmm_(ext_a, ext_b.t())
-        w = _nf4_dequant_bf16(base) if (base.kernel_ok() and x.is_cuda) else dequantize_nf4(base, x.dtype)
+        w = _nf4_expand(base) if (base.kernel_ok() and x.is_cuda) else dequantize_nf4(base, x.dtype)
         return _base_gemm(x, w, ext_a, ext_b, residual)
     M, K = x.shape
     N = base.shape[0]
@@ -207,6 +238,6 @@ def _base_gemm_t(dy, base, ext_a=None, ext_b=None, c=None):
         if _w4_ok(dy, base, True):
             dx = _w4_gemm(dy, base, True, c)
             return dx if ext_a is None else dx.addmm_(ext_a, ext_b.t())
-        base = _nf4_dequant_bf16(base) if (base.kernel_ok() and dy.is_cuda) else dequantize_nf4(base, dy.dtype)
+        base = _nf4_expand(base) if (base.kernel_ok() and dy.is_cuda) else dequantize_nf4(base, dy.dtype)
     dx = _dense_dx(dy, base, c)
     return dx if ext_a is None else dx.addmm_(ext_a, ext_b.t())

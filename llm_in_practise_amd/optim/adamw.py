@@ -137,7 +137,7 @@ class _FlatOptimizer:
     def zero_grad(self, set_to_none: bool = False):
         self.flat.zero_grad()
         # a clip_grad_norm_ that no step() followed (a logged-only norm, a skipped step) must not let the next
-        # step() skip its own sync_grads / NF4-cache release
+        # step() skip its own sync_grads
         self._prepared = False
 
     @property
@@ -146,9 +146,9 @@ class _FlatOptimizer:
 
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
         """Global L2 norm of the flat grads + clip coefficient, on the device.  The host-side step preparation
-        (separately allocated grads folded into the flat buffer — which the norm must include — and the NF4
-        expansion cache released) runs here, before the norm launches, so step() is one launch per group
-        right behind them."""
+        (separately allocated grads folded into the flat buffer — which the norm must include) runs here, before
+        the norm launches, so step() is one launch per group right behind them.  (``nf4_cache_advance`` is the
+        step hook of the NF4 expansions; they are resident now and it does nothing.)"""
         self.max_grad_norm = max_norm
         nf4_cache_advance()
         self.flat.sync_grads()

@@ -161,6 +161,8 @@ class _QuantFlat:
     def __init__(self, tensors, owners, world, rank, device):
         self.tensors, self.owners = tensors, owners
         self.world, self.rank = world, rank
+        for q in owners:      # gathered and released every step: a resident expansion would pin the gathered bytes
+            q.resident = False
         segs, total = {}, 0
         for t in tensors:
             st = t.untyped_storage()
@@ -733,7 +735,7 @@ class ZeroEngine:
         if not boundary:
             return
         from ..ops.linear import nf4_cache_advance
-        nf4_cache_advance()        # the step's NF4 expansions (checkpointed layers) are released
+        nf4_cache_advance()        # (a no-op since the expansions are resident: ops/gemm.py)
         self._optimizer_step()
         self.global_steps += 1
         if self.lr_scheduler is not None:

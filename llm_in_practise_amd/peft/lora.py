@@ -25,6 +25,7 @@ from typing import Iterable
 import torch
 import torch.nn as nn
 
+from ..ops.gemm import nf4_resident_clear
 from ..ops.linear import LoraBranch, fused_linear
 from ..quant.nf4 import NF4Weight, dequantize_nf4, quantize_nf4
 
@@ -67,8 +68,10 @@ class Linear4bit(nn.Module):
     def nf4(self) -> NF4Weight:
         c = self.__dict__.get("_nf4_cache")
         if c is None or c.codes is not self.codes:
+            # module-owned: the expansion stays resident (unless an owner such as ZeRO-3 turned that off)
             c = NF4Weight(self.codes, self.absmax, self.qabsmax, self.absmax2, self.offset,
-                          (self.out_features, self.in_features), self.blocksize, self.compute_dtype)
+                          (self.out_features, self.in_features), self.blocksize, self.compute_dtype,
+                          resident=c.resident if c is not None else True)
             self.__dict__["_nf4_cache"] = c
         return c
 
@@ -342,6 +345,7 @@ class PeftModel(nn.Module):
                 setattr(parent, leaf, mod.merge())
         if hasattr(model, "invalidate_fusion"):
             model.invalidate_fusion()
+        nf4_resident_clear()        # the merged bases are gone: their resident bf16 expansions go now, not at GC
         return model
 
 

@@ -92,6 +92,10 @@ class NF4Weight:
     shape: tuple[int, int]
     blocksize: int = 64
     dtype: torch.dtype = torch.bfloat16   # compute / dequant dtype
+    # a module-owned frozen base (Linear4bit / fused-projection bases of a quantised or loaded model): its bf16
+    # expansion is kept resident by the native registry (ops/gemm.py ``_nf4_expand``).  Off for temporaries,
+    # which a kept reference would pin: weights quantised by hand, ZeRO-3's gathered partitions.
+    resident: bool = False
 
     @property
     def double_quant(self) -> bool:
@@ -186,7 +190,7 @@ def double_quantize_absmax(q: NF4Weight) -> NF4Weight:
     dcode = dynamic_code(str(absmax.device))
     qabs = _nearest(grp / absmax2[:, None], dcode).view(-1)[:nb].contiguous()
     offs = offset.expand(ng).contiguous()
-    return NF4Weight(q.codes, None, qabs, absmax2.contiguous(), offs, q.shape, q.blocksize, q.dtype)
+    return NF4Weight(q.codes, None, qabs, absmax2.contiguous(), offs, q.shape, q.blocksize, q.dtype, q.resident)
 
 
 def dequantize_nf4(q: NF4Weight, dtype: torch.dtype | None = None) -> torch.Tensor:
@@ -209,12 +213,13 @@ def concat_nf4(parts: list[NF4Weight]) -> NF4Weight:
     dq = parts[0].double_quant
     assert all(p.double_quant == dq for p in parts)
     n = sum(p.shape[0] for p in parts)
+    resident = all(p.resident for p in parts)
     codes = torch.cat([p.codes for p in parts], 0)
     if dq:
         for p in parts:
             assert p.qabsmax.numel() % DQ_GROUP == 0, "part not group aligned"
         return NF4Weight(codes, None, torch.cat([p.qabsmax for p in parts]),
                          torch.cat([p.absmax2 for p in parts]), torch.cat([p.offset for p in parts]),
-                         (n, k), parts[0].blocksize, parts[0].dtype)
+                         (n, k), parts[0].blocksize, parts[0].dtype, resident)
     return NF4Weight(codes, torch.cat([p.absmax for p in parts]), None, None, None,
-                     (n, k), parts[0].blocksize, parts[0].dtype)
+                     (n, k), parts[0].blocksize, parts[0].dtype, resident)

@@ -52,13 +52,14 @@ def _merged_model(name: str, r: int, alpha: int, seed: int, device):
 
 
 @torch.no_grad()
-def _decode_steps(lm, batches, ctx, steps, max_len):
+def _decode_steps(lm, batches, ctx, steps, max_len, kv_dtype=None):
     from ..infer.graphs import DecodeGraphs
     from ..models.common import KVCache
     cfg = lm.config
     dev = next(lm.parameters()).device
     B = max(batches)
-    cache = KVCache(cfg.num_hidden_layers, B, max_len, cfg.num_key_value_heads, cfg.head_dim, torch.bfloat16, dev)
+    cache = KVCache(cfg.num_hidden_layers, B, max_len, cfg.num_key_value_heads, cfg.head_dim, torch.bfloat16, dev,
+                    kv_dtype=kv_dtype)
     cache.pos = torch.full((B,), ctx, dtype=torch.long, device=dev)
     tok = torch.randint(0, cfg.vocab_size, (B,), device=dev)
     if dev.type == "cuda":                         # hipGraph replay, as the serving engine decodes
@@ -153,6 +154,8 @@ def main(argv=None):
     ap.add_argument("--serve-tokens", type=int, default=256)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp8", action="store_true", help="also measure an FP8 W8A8 copy of the model (quant/fp8.py)")
+    ap.add_argument("--kv-fp8", action="store_true",
+                    help="also time the bf16 model's decode steps over an FP8 KV cache (--kv-cache-dtype fp8)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     from ..quant.eval import self_ppl
@@ -173,6 +176,10 @@ def main(argv=None):
                    "self_ppl": self_ppl(lm, prompts, a.ppl_new),
                    "weight_bytes": sum(p.numel() * p.element_size() for n, p in lm.named_parameters()
                                        if n.startswith("model.layers") and p.dim() == 2)}
+    if a.kv_fp8:       # the same bf16 weights over an FP8 (e4m3) KV cache, same process, right after the bf16 cache
+        res["bf16_kv_fp8"] = {"decode": _decode_steps(lm, a.batches, a.ctx, a.steps, a.max_len, kv_dtype="fp8")}
+        res["kv_fp8_decode_speedup"] = {str(b["batch"]): round(b["step_ms"] / q["step_ms"], 3)
+                                        for b, q in zip(res["bf16"]["decode"], res["bf16_kv_fp8"]["decode"])}
     ref_logp = _next_token_logp(lm, eval_ids)
     lm.invalidate_fusion()
 

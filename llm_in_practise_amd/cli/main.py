@@ -469,6 +469,21 @@ _VLLM_QUANT = {"awq": ("awq", "compressed-tensors"), "awq_marlin": ("awq", "comp
                "compressed-tensors": ("compressed-tensors", "awq", "gptq")}
 
 
+def _kv_cache_dtype_compat(a):
+    """``--kv-cache-dtype`` (vLLM flag): every spelling → ``a.kv_cache_dtype`` ∈ {"bf16", "fp8"}; the combinations
+    the FP8 cache does not serve are refused here, before a model is loaded (the engine checks the head dim)."""
+    from ..infer.engine import check_kv_fp8_config
+    from ..models.common import normalize_kv_dtype
+    try:
+        a.kv_cache_dtype = normalize_kv_dtype(getattr(a, "kv_cache_dtype", None))
+        if a.kv_cache_dtype == "fp8":
+            check_kv_fp8_config(128, tp=int(getattr(a, "tp", None) or 1), pp=int(getattr(a, "pp", None) or 1),
+                                kv_remote=bool(getattr(a, "kv_remote_url", None) or getattr(a, "kv_transfer_config", None)))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return a
+
+
 def _vllm_compat(a):
     """Map vLLM's ``vllm serve`` flags onto ``lipa serve`` so the reference's manifests apply unchanged
     (``LLM_on_Kubernetes/Inference_Platfrom/01-Base/vLLM/vllm-deployment.yaml:97-114``, the litellm-proxy compose
@@ -510,6 +525,7 @@ def _vllm_compat(a):
                 a.quant = "fp8"
     if getattr(a, "quant", None) == "fp8" and max(int(getattr(a, "tp", None) or 1), int(getattr(a, "pp", None) or 1)) > 1:
         raise SystemExit(_FP8_NO_TP)
+    _kv_cache_dtype_compat(a)
     if vq == "bitsandbytes":
         a.quant = "nf4"
     elif vq is not None and vq != "fp8":
@@ -566,7 +582,7 @@ def _serving_engine_from_args(a, tp=None, tpg=None, ppg=None):
                          chunked_prefill=g("max_batched_tokens", 2048) if g("chunked_prefill") else 0,
                          lora_modules=loras, host_cache_blocks=host_blocks,
                          kv_remote_url=g("kv_remote_url"), gpu_memory_utilization=g("gpu_memory_utilization"),
-                         use_graphs=False if g("enforce_eager") else None)
+                         use_graphs=False if g("enforce_eager") else None, kv_cache_dtype=g("kv_cache_dtype"))
 
 
 def _serve_task(a) -> str:
@@ -1069,6 +1085,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="vLLM flag: int4 / FP8 checkpoints load by their quantization_config; bitsandbytes = NF4; "
                         "fp8 = dynamic W8A8 (e4m3) quantised after a bf16 load")
     p.add_argument("--dtype", default="auto", choices=["auto", "bfloat16", "bf16", "half", "float16", "float32"])
+    p.add_argument("--kv-cache-dtype", "--kv_cache_dtype", dest="kv_cache_dtype", default="auto",
+                   help="vLLM flag: auto | bfloat16 (the model's dtype) or fp8 | fp8_e4m3 (e4m3 codes and one scale "
+                        "per token and kv head: 0.5625 of the bf16 cache bytes; one GPU, head dim 64 / 128)")
     p.add_argument("--gpu-memory-utilization", dest="gpu_memory_utilization", type=float, default=None,
                    help="vLLM flag: fraction of device memory for weights + KV; sizes the KV slot pool")
     p.add_argument("--host", default="0.0.0.0")

@@ -127,6 +127,11 @@ int decode_split_plan(int, int, int);
 int decode_split_plan2(int, int, int);
 void launch_decode_attention2(const void*, int, const void*, int, const void*, int, void*, void*, const int64_t*, float*,
                               float*, float*, void*, int, int, int, int, int, int, float, hipStream_t);
+void launch_decode_attention_fp8(const void*, int, const void*, int, const void*, int, void*, void*, const int64_t*, float*,
+                                 float*, float*, void*, int, int, int, int, int, int, float, hipStream_t);
+void launch_kv_fp8_write_rows(const void*, long, const void*, long, void*, void*, const int64_t*, long, int, int, long,
+                              hipStream_t);
+void launch_kv_fp8_dequant_rows(const void*, long, void*, long, int, int, hipStream_t);
 void launch_sample(int, const void*, const int*, int, float*, int64_t*, int, int, float, int, float, float, uint64_t,
                    hipStream_t);
 void launch_sample_logprobs(int, const void*, const int*, int, float*, int64_t*, float*, int64_t*, float*, int, int, int,
@@ -1834,6 +1839,92 @@ Tensor decode_attention_append(Tensor q, Tensor knew, Tensor vnew, Tensor kc, Te
   return out;
 }
 
+// ---- FP8 (e4m3) KV cache (kernels/kvcache_fp8.hip).  Cache tensors are uint8 [.., Hkv*(D+16)]: per kv head D codes and
+// a 16-byte tail that starts with the fp32 scale.
+void check_kv_fp8_dims(const char* who, int64_t hkv, int64_t d) {
+  TORCH_CHECK(d == 64 || d == 128, who, ": head_dim 64 or 128");
+  TORCH_CHECK(hkv >= 1, who, ": hkv >= 1");
+}
+void check_kv_fp8_cache(const char* who, const Tensor& c, int64_t hkv, int64_t d) {
+  TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kByte, who, ": the cache is a uint8 GPU tensor");
+  TORCH_CHECK(c.dim() >= 2 && c.size(-1) == hkv * (d + 16), who, ": cache row width must be hkv * (head_dim + 16) = ",
+              hkv * (d + 16), ", got ", c.dim() ? c.size(-1) : 0);
+  TORCH_CHECK(c.is_contiguous(), who, ": the cache must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0, who, ": the cache must be 16-byte aligned");
+}
+void check_kv_fp8_rows(const char* who, const Tensor& t, int64_t rows, int64_t width) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, who, ": bf16 GPU rows");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == width && t.stride(1) == 1 && t.stride(0) % 8 == 0 &&
+                  t.stride(0) >= width && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              who, ": 2-D row-strided [", rows, ", ", width, "] rows, 16-byte aligned");
+}
+
+// q [B, hq*d], knew/vnew [B, hkv*d] bf16 (row-strided views allowed), caches uint8 [B, Smax, hkv*(d+16)], pos [B] int64:
+// quantises knew/vnew into the caches at pos and attends over the pos + 1 dequantised keys
+Tensor decode_attention_append_fp8(Tensor q, Tensor knew, Tensor vnew, Tensor kc, Tensor vc, Tensor pos, int64_t hq,
+                                   int64_t hkv, int64_t d, int64_t max_len, double scale) {
+  const char* who = "decode_attention_append_fp8";
+  check_kv_fp8_dims(who, hkv, d);
+  TORCH_CHECK(hq % hkv == 0 && hq / hkv <= 16, who, ": group size hq / hkv <= 16");
+  TORCH_CHECK(q.dim() == 2, who, ": q is [B, hq*d]");
+  const int64_t B = q.size(0);
+  check_kv_fp8_rows(who, q, B, hq * d);
+  check_kv_fp8_rows(who, knew, B, hkv * d);
+  check_kv_fp8_rows(who, vnew, B, hkv * d);
+  check_kv_fp8_cache(who, kc, hkv, d);
+  check_kv_fp8_cache(who, vc, hkv, d);
+  TORCH_CHECK(kc.dim() == 3 && kc.size(0) == B && vc.sizes() == kc.sizes(), who, ": caches are [B, Smax, hkv*(d+16)]");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.is_contiguous() && pos.numel() == B, who,
+              ": pos is int64 [B]");
+  const int64_t Smax = kc.size(1);
+  TORCH_CHECK(max_len >= 1 && max_len <= Smax, who, ": max_len outside the cache");
+  TORCH_CHECK(B >= 1 && B <= 65535 && hkv <= 65535, who, ": grid limits");
+  const int nsplit = decode_split_plan2(B, hkv, max_len);
+  auto f32 = q.options().dtype(at::kFloat);
+  Tensor opart = at::empty({B * hq * nsplit, d}, f32);
+  Tensor mpart = at::empty({B * hq * nsplit}, f32), lpart = at::empty({B * hq * nsplit}, f32);
+  Tensor out = at::empty({B, hq * d}, q.options());
+  launch_decode_attention_fp8(q.data_ptr(), q.stride(0), knew.data_ptr(), knew.stride(0), vnew.data_ptr(),
+                              vnew.stride(0), kc.data_ptr(), vc.data_ptr(), pos.data_ptr<int64_t>(),
+                              opart.data_ptr<float>(), mpart.data_ptr<float>(), lpart.data_ptr<float>(), out.data_ptr(),
+                              B, Smax, hq, hkv, d, nsplit, (float)scale, stream());
+  return out;
+}
+
+// k/v [T, hkv*d] bf16 (row-strided) quantised into cache rows idx [T] (int64) of kc/vc seen as [R, hkv*(d+16)]
+void kv_fp8_write_rows(Tensor k, Tensor v, Tensor kc, Tensor vc, Tensor idx, int64_t hkv, int64_t d) {
+  const char* who = "kv_fp8_write_rows";
+  check_kv_fp8_dims(who, hkv, d);
+  TORCH_CHECK(k.dim() == 2, who, ": k is [T, hkv*d]");
+  const int64_t T = k.size(0);
+  check_kv_fp8_rows(who, k, T, hkv * d);
+  check_kv_fp8_rows(who, v, T, hkv * d);
+  check_kv_fp8_cache(who, kc, hkv, d);
+  check_kv_fp8_cache(who, vc, hkv, d);
+  TORCH_CHECK(vc.numel() == kc.numel(), who, ": k and v caches of one size");
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kLong && idx.is_contiguous() && idx.numel() == T, who,
+              ": idx is int64 [T]");
+  const int64_t R = kc.numel() / (hkv * (d + 16));
+  launch_kv_fp8_write_rows(k.data_ptr(), (long)k.stride(0), v.data_ptr(), (long)v.stride(0), kc.data_ptr(),
+                           vc.data_ptr(), idx.data_ptr<int64_t>(), (long)T, (int)hkv, (int)d, (long)R, stream());
+}
+
+// cache rows [n, hkv*(d+16)] uint8 (row-strided) → bf16 [n, hkv*d]
+Tensor kv_fp8_dequant_rows(Tensor rows, int64_t hkv, int64_t d) {
+  const char* who = "kv_fp8_dequant_rows";
+  check_kv_fp8_dims(who, hkv, d);
+  TORCH_CHECK(rows.is_cuda() && rows.scalar_type() == at::kByte && rows.dim() == 2, who, ": uint8 GPU rows [n, W]");
+  TORCH_CHECK(rows.size(1) == hkv * (d + 16), who, ": row width must be hkv * (head_dim + 16) = ", hkv * (d + 16),
+              ", got ", rows.size(1));
+  TORCH_CHECK(rows.stride(1) == 1 && rows.stride(0) % 16 == 0 && rows.stride(0) >= rows.size(1) &&
+                  reinterpret_cast<uintptr_t>(rows.data_ptr()) % 16 == 0,
+              who, ": rows must be 16-byte aligned");
+  Tensor out = at::empty({rows.size(0), hkv * d}, rows.options().dtype(at::kBFloat16));
+  launch_kv_fp8_dequant_rows(rows.data_ptr(), (long)rows.stride(0), out.data_ptr(), (long)rows.size(0), (int)hkv,
+                             (int)d, stream());
+  return out;
+}
+
 // logits [B, V] fp32|bf16; hist [B, L] int32 (-1 = pad) or None; temperature <= 0 → greedy
 Tensor sample(Tensor logits, optional<Tensor> hist, double temperature, int64_t top_k, double top_p, double penalty,
               int64_t key) {
@@ -2142,6 +2233,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_norm", &grad_norm);
   m.def("decode_attention", &decode_attention);
   m.def("decode_attention_append", &decode_attention_append);
+  m.def("decode_attention_append_fp8", &decode_attention_append_fp8);
+  m.def("kv_fp8_write_rows", &kv_fp8_write_rows);
+  m.def("kv_fp8_dequant_rows", &kv_fp8_dequant_rows);
   m.def("lora_proj", &lora_proj);
   m.def("lora_acc", &lora_acc);
   m.def("lora_proj2", &lora_proj2);

@@ -35,7 +35,8 @@ EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX")
 # Per-source hipcc flags.  fp8.hip is built with the packed fp32 VALU forms (v_pk_{add,mul,fma}_f32) off: a policy
 # for kernels added from this file on, so that their fp32 epilogues and fixed-order sums compile to the scalar
 # instructions the source spells out.  Per lane the result is the same IEEE operation.
-_EXTRA_KFLAGS = {"fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+_EXTRA_KFLAGS = {"fp8.hip": _NO_PK_F32, "kvcache_fp8.hip": _NO_PK_F32}
 
 
 def _torch_flags():

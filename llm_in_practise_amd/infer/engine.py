@@ -32,7 +32,7 @@ from typing import Any
 
 import torch
 
-from ..models.common import KVCache, PackedPrefill
+from ..models.common import KVCache, PackedPrefill, normalize_kv_dtype
 from ..ops.decode import MAX_LOGIT_BIAS, MAX_LOGPROBS, sample, sample_logprobs, sample_rows, seed_key
 from ..ops.linear import head_logits
 from ..train.data import render_chatml
@@ -380,6 +380,25 @@ def kv_slots_for_budget(total_bytes: int, used_bytes: int, fraction: float, slot
     return int(budget // slot_bytes)
 
 
+def kv_token_bytes(n_layers: int, hkv: int, d: int, elt: int = 2, fp8: bool = False) -> int:
+    """HBM bytes one cached token costs over all layers (K and V).  The FP8 cache stores ``d`` codes and a
+    16-byte scale tail per head: 0.5625 of the bf16 bytes at ``d`` = 128."""
+    return 2 * n_layers * hkv * ((d + 16) if fp8 else d * elt)
+
+
+def check_kv_fp8_config(head_dim: int, tp: int = 1, pp: int = 1, kv_remote: bool = False):
+    """Start-up rejections of ``--kv-cache-dtype fp8``; every message names the flag."""
+    if tp > 1:
+        raise ValueError("--kv-cache-dtype fp8 does not support --tensor-parallel-size > 1")
+    if pp > 1:
+        raise ValueError("--kv-cache-dtype fp8 does not support --pipeline-parallel-size > 1")
+    if kv_remote:
+        raise ValueError("--kv-cache-dtype fp8 does not support --kv-remote-url / --kv-transfer-config "
+                         "(the remote KV store holds bf16 rows)")
+    if head_dim not in (64, 128):
+        raise ValueError(f"--kv-cache-dtype fp8 needs a head dim of 64 or 128, the model has {head_dim}")
+
+
 class ServingEngine:
     def __init__(self, model, tokenizer, model_name: str = "lipa-model", max_batch: int = 16,
                  system_prompt: str | None = None, chat_template: str = "auto", space_before_end: bool = False,
@@ -387,8 +406,11 @@ class ServingEngine:
                  use_graphs: bool | None = None, tp_group=None, prefix_cache_blocks: int = 0,
                  prefix_block: int = 64, chunked_prefill: int = 0, lora_modules: dict[str, str] | None = None,
                  host_cache_blocks: int = 0, kv_remote_url: str | None = None,
-                 gpu_memory_utilization: float | None = None):
-        """``tp_group``: the model was sharded by ``parallel.tensor_parallel`` over this group.
+                 gpu_memory_utilization: float | None = None, kv_cache_dtype: str | None = None):
+        """``kv_cache_dtype``: ``--kv-cache-dtype`` (``auto`` / ``bfloat16``: the model's dtype; ``fp8`` /
+        ``fp8_e4m3``: e4m3 codes with a scale per token and kv head, ``ops/kv_fp8.py``).
+
+        ``tp_group``: the model was sharded by ``parallel.tensor_parallel`` over this group.
         The engine then runs SPMD — group rank 0 owns the request queue and broadcasts each
         iteration's admissions; the other ranks call :meth:`follower_loop` and replay exactly the
         same prefill / decode / sampling (logits are bit-identical across ranks, the samplers
@@ -440,10 +462,15 @@ class ServingEngine:
         self.h_latency = _Histogram([0.05, 0.1, 0.25, 0.5, 1, 2, 5, 10, 30, 60])
         self.h_ttft = _Histogram([0.01, 0.025, 0.05, 0.1, 0.2, 0.5, 1, 2, 5])
         self.queue_time_ewma: float | None = None
+        self.kv_fp8 = normalize_kv_dtype(kv_cache_dtype) == "fp8"
+        if self.kv_fp8:
+            check_kv_fp8_config(cfg.head_dim, tp=1 if tp_group is None else 2,
+                                pp=2 if getattr(self.lm.model, "pp", None) is not None else 1,
+                                kv_remote=bool(kv_remote_url))
         if gpu_memory_utilization is not None and self.device.type == "cuda":
             # the KV pool sized from the memory fraction (vLLM --gpu-memory-utilization), capped by max_batch
-            elt = torch.finfo(self.lm.lm_head.weight.dtype).bits // 8
-            slot = 2 * cfg.num_hidden_layers * self.max_len * cfg.num_key_value_heads * cfg.head_dim * elt
+            slot = self.max_len * kv_token_bytes(cfg.num_hidden_layers, cfg.num_key_value_heads, cfg.head_dim,
+                                                 torch.finfo(self.lm.lm_head.weight.dtype).bits // 8, self.kv_fp8)
             reserve = (2 << 30) + prefill_token_budget * (16 * cfg.hidden_size + 6 * getattr(cfg, "intermediate_size", 0))
             fit = kv_slots_for_budget(torch.cuda.get_device_properties(self.device).total_memory,
                                       torch.cuda.memory_allocated(self.device), gpu_memory_utilization, slot, reserve)
@@ -451,7 +478,7 @@ class ServingEngine:
             self.max_batch = max_batch
             self.max_prefill_batch = min(self.max_prefill_batch, max_batch)
         self.cache = KVCache(cfg.num_hidden_layers, max_batch, self.max_len, cfg.num_key_value_heads, cfg.head_dim,
-                             self.lm.lm_head.weight.dtype, self.device)
+                             self.lm.lm_head.weight.dtype, self.device, kv_dtype="fp8" if self.kv_fp8 else None)
         self.cache.pos = torch.zeros(max_batch, dtype=torch.long, device=self.device)
         self.prefix = None
         remote = None
@@ -459,8 +486,9 @@ class ServingEngine:
             from .kv_server import RemoteKV
             remote = RemoteKV(kv_remote_url)
         if prefix_cache_blocks > 0:
-            self.prefix = PrefixCache(cfg.num_hidden_layers, cfg.num_key_value_heads * cfg.head_dim,
-                                      self.lm.lm_head.weight.dtype, self.device, prefix_block, prefix_cache_blocks,
+            # row width and dtype are the cache's: FP8 rows move as bytes, codes and scales together
+            self.prefix = PrefixCache(cfg.num_hidden_layers, self.cache.k[0].shape[-1],
+                                      self.cache.k[0].dtype, self.device, prefix_block, prefix_cache_blocks,
                                       host_blocks=host_cache_blocks, remote=remote,
                                       namespace=self._kv_namespace(prefix_block))
         # multi-LoRA serving (vLLM --enable-lora --lora-modules): stacked adapters, per-row masks;
@@ -525,6 +553,8 @@ class ServingEngine:
         h = hashlib.blake2b(digest_size=16)
         h.update(f"{self.model_name}|{cfg.num_hidden_layers}|{cfg.num_key_value_heads}|{cfg.head_dim}|"
                  f"{self.lm.lm_head.weight.dtype}|{block}|tp{self.tp_rank}".encode())
+        if self.kv_fp8:
+            h.update(b"|kv-fp8-e4m3")
         params = list(self.lm.parameters())
         with torch.no_grad():
             for p in (params[0], params[-1], self.lm.lm_head.weight):
@@ -747,6 +777,7 @@ class ServingEngine:
 
     def _slot_view(self, slot: int, length: int) -> KVCache:
         view = KVCache.__new__(KVCache)
+        view.fp8, view.hkv, view.d = self.cache.fp8, self.cache.hkv, self.cache.d
         view.k = [t[slot:slot + 1] for t in self.cache.k]
         view.v = [t[slot:slot + 1] for t in self.cache.v]
         view.len, view.max_len, view.batch, view.pos = length, self.cache.max_len, 1, None

@@ -38,6 +38,7 @@ class GenerationConfig:
     pad_token_id: int | None = None
     seed: int | None = None
     sync_every: int = 8          # host check for "all rows finished" every N tokens
+    kv_cache_dtype: str | None = None    # "fp8" / "fp8_e4m3": FP8 KV cache (ops/kv_fp8.py); None / "auto": the model's dtype
 
     @classmethod
     def from_kwargs(cls, base: "GenerationConfig | None" = None, **kw) -> "GenerationConfig":
@@ -81,7 +82,8 @@ def generate(model, input_ids: torch.Tensor, attention_mask: torch.Tensor | None
     mcfg = lm.config
     n_layers = mcfg.num_hidden_layers
     hkv, d = mcfg.num_key_value_heads, mcfg.head_dim
-    cache = KVCache(n_layers, B, S + cfg.max_new_tokens, hkv, d, lm.lm_head.weight.dtype, dev)
+    cache = KVCache(n_layers, B, S + cfg.max_new_tokens, hkv, d, lm.lm_head.weight.dtype, dev,
+                    kv_dtype=cfg.kv_cache_dtype)
     temperature = cfg.temperature if cfg.do_sample else 0.0
     if cfg.seed is not None:
         from ..ops.decode import seed_sampler

@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 
 from ..ops.attention import flash_attention_varlen, native_ok
+from ..ops.kv_fp8 import HEAD_DIMS as FP8_KV_HEAD_DIMS, kv_fp8_dequant_rows, kv_fp8_write_rows, row_bytes
 from ..ops.linear import LoraBranch, fused_linear
 from ..peft.lora import Linear4bit, LoraLayer, base_of
 from ..quant.fp8 import Fp8Linear, Fp8Weight, fp8_linear
@@ -198,6 +199,22 @@ def can_fuse(mods: list[nn.Module]) -> bool:
     return False
 
 
+KV_CACHE_DTYPES = ("auto", "bfloat16", "fp8", "fp8_e4m3")
+
+
+def normalize_kv_dtype(name: str | None) -> str:
+    """``--kv-cache-dtype`` spellings → ``"bf16"`` (``auto`` / ``bfloat16``: the model's dtype, the code path as it
+    was) or ``"fp8"`` (``fp8`` / ``fp8_e4m3`` / ``fp8-e4m3``)."""
+    n = (name or "auto").lower().replace("-", "_")
+    if n in ("auto", "bfloat16", "bf16"):
+        return "bf16"
+    if n in ("fp8", "fp8_e4m3"):
+        return "fp8"
+    if n == "fp8_e5m2":
+        raise ValueError("--kv-cache-dtype fp8_e5m2 is not supported: the FP8 KV cache is e4m3 (fp8 / fp8_e4m3)")
+    raise ValueError(f"--kv-cache-dtype {name}: expected one of {', '.join(KV_CACHE_DTYPES)}")
+
+
 class PackedPrefill:
     """Prefill of several prompts packed back to back — ``[1, T]`` tokens, no padding — straight
     into their KV-cache slots (the serving engine's admission path).
@@ -225,8 +242,16 @@ class PackedPrefill:
         self.cu_seqlens = torch.tensor(self.cu_host, dtype=torch.int32, device=device)
 
     def attend(self, layer: int, q, k, v, hq: int, hkv: int, d: int, attention_fn):
-        self.cache.k[layer].view(-1, hkv * d).index_copy_(0, self.cache_idx, k)
-        self.cache.v[layer].view(-1, hkv * d).index_copy_(0, self.cache_idx, v)
+        if self.cache.fp8:
+            # quantised into the slots and read back: the prompts attend over the K/V bits every later step, a
+            # later chunk or a prefix hit will see
+            ck, cv = self.cache.k[layer], self.cache.v[layer]
+            kv_fp8_write_rows(k, v, ck, cv, self.cache_idx, hkv, d)
+            k = kv_fp8_dequant_rows(ck.view(-1, ck.shape[-1]).index_select(0, self.cache_idx), hkv, d)
+            v = kv_fp8_dequant_rows(cv.view(-1, cv.shape[-1]).index_select(0, self.cache_idx), hkv, d)
+        else:
+            self.cache.k[layer].view(-1, hkv * d).index_copy_(0, self.cache_idx, k)
+            self.cache.v[layer].view(-1, hkv * d).index_copy_(0, self.cache_idx, v)
         if self.B == 1:
             return attention_fn(q, k, v, 1, self.S, hq, hkv, d, causal=True, kv_lens=None)
         if native_ok(q, d):
@@ -246,11 +271,23 @@ class KVCache:
     Prefill writes a uniform prefix (``update``; rows may be right-padded, their valid lengths
     live in ``lens``); decode appends one token per row at its own position ``pos[b]``
     (``write_rows``), so a batch of prompts of different lengths decodes without re-padding.
-    ``pos`` is a device tensor, so a decode step has no host sync (hipGraph-capturable)."""
+    ``pos`` is a device tensor, so a decode step has no host sync (hipGraph-capturable).
 
-    def __init__(self, n_layers: int, batch: int, max_len: int, hkv: int, d: int, dtype, device):
-        self.k = [torch.zeros(batch, max_len, hkv * d, dtype=dtype, device=device) for _ in range(n_layers)]
-        self.v = [torch.zeros(batch, max_len, hkv * d, dtype=dtype, device=device) for _ in range(n_layers)]
+    ``kv_dtype="fp8"``: rows are ``uint8 [Hkv*(D+16)]`` — per head D e4m3 codes and a 16-byte tail that starts
+    with the fp32 scale (``ops/kv_fp8.py``), 0.5625 of the bf16 bytes at D = 128.  Writes quantise; the decode
+    step runs ``decode_attention_append_fp8`` on the codes; a prefix read dequantises the rows it needs."""
+
+    def __init__(self, n_layers: int, batch: int, max_len: int, hkv: int, d: int, dtype, device,
+                 kv_dtype: str | None = None):
+        self.fp8 = normalize_kv_dtype(kv_dtype) == "fp8"
+        self.hkv, self.d = hkv, d
+        width = hkv * d
+        if self.fp8:
+            if d not in FP8_KV_HEAD_DIMS:
+                raise ValueError(f"--kv-cache-dtype fp8 needs a head dim of 64 or 128, the model has {d}")
+            width, dtype = row_bytes(hkv, d), torch.uint8
+        self.k = [torch.zeros(batch, max_len, width, dtype=dtype, device=device) for _ in range(n_layers)]
+        self.v = [torch.zeros(batch, max_len, width, dtype=dtype, device=device) for _ in range(n_layers)]
         self.len = 0
         self.max_len = max_len
         self.batch = batch
@@ -260,14 +297,32 @@ class KVCache:
     def update(self, layer: int, k: torch.Tensor, v: torch.Tensor, start: int):
         """k/v [B, s, Hkv*D] written at ``start``; returns views up to start+s."""
         s = k.shape[1]
-        self.k[layer][:, start:start + s] = k
-        self.v[layer][:, start:start + s] = v
+        if self.fp8:
+            idx = (self._rows[:, None] * self.max_len + (start + torch.arange(s, device=k.device))[None]).reshape(-1)
+            kv_fp8_write_rows(k.reshape(-1, k.shape[-1]), v.reshape(-1, v.shape[-1]), self.k[layer], self.v[layer],
+                              idx, self.hkv, self.d)
+        else:
+            self.k[layer][:, start:start + s] = k
+            self.v[layer][:, start:start + s] = v
         return self.k[layer][:, :start + s], self.v[layer][:, :start + s]
 
     def write_rows(self, layer: int, k: torch.Tensor, v: torch.Tensor):
         """k/v [B, Hkv*D] written at row-specific positions ``pos``."""
+        if self.fp8:
+            kv_fp8_write_rows(k, v, self.k[layer], self.v[layer], self._rows * self.max_len + self.pos, self.hkv, self.d)
+            return
         self.k[layer][self._rows, self.pos] = k
         self.v[layer][self._rows, self.pos] = v
+
+    def prefix_bf16(self, layer: int, n: int):
+        """FP8 cache: the first ``n`` rows of every slot of this (view of the) cache expanded to bf16
+        ``[B, n, Hkv*D]`` — the transient the bf16 prefix attention kernel reads; freed by the caller's scope."""
+        B = self.k[layer].shape[0]
+        out = []
+        for c in (self.k[layer], self.v[layer]):
+            rows = c[:, :n].reshape(B * n, c.shape[-1])       # a view for one slot, a copy of the live rows otherwise
+            out.append(kv_fp8_dequant_rows(rows, self.hkv, self.d).view(B, n, self.hkv * self.d))
+        return out
 
     def head_rows(self, n: int) -> "KVCache":
         """View of the first ``n`` rows sharing storage (and ``pos``) with this cache — the serving
@@ -275,6 +330,7 @@ class KVCache:
         if n == self.batch:
             return self
         v = KVCache.__new__(KVCache)
+        v.fp8, v.hkv, v.d = self.fp8, self.hkv, self.d
         v.k = [t[:n] for t in self.k]
         v.v = [t[:n] for t in self.v]
         v.len, v.max_len, v.batch = self.len, self.max_len, n

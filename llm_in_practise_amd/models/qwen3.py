@@ -29,6 +29,7 @@ from ..ops.activation import swiglu_fused
 from ..ops.mlp import fusable as mlp_fusable, swiglu_mlp
 from ..ops.attention import check_cu_seqlens, flash_attention, flash_attention_prefix, flash_attention_varlen
 from ..ops.decode import decode_attention_append
+from ..ops.kv_fp8 import decode_attention_append_fp8
 from ..ops.linear import checkpoint as lora_checkpoint
 from ..ops.loss import fused_linear_cross_entropy, shift_labels
 from ..ops.norm import RMSNorm, rms_norm, rms_norm_residual
@@ -129,6 +130,10 @@ PRESETS: dict[str, dict] = {
     "qwen3-tiny": dict(vocab_size=512, hidden_size=128, intermediate_size=256, num_hidden_layers=2,
                        num_attention_heads=4, num_key_value_heads=2, head_dim=32,
                        max_position_embeddings=512),
+    # qwen3-tiny with the smallest head dim the decode / FP8-KV kernels serve
+    "qwen3-tiny-d64": dict(vocab_size=512, hidden_size=128, intermediate_size=256, num_hidden_layers=2,
+                           num_attention_heads=4, num_key_value_heads=2, head_dim=64,
+                           max_position_embeddings=512),
     "qwen3-small": dict(vocab_size=4096, hidden_size=1024, intermediate_size=3072, num_hidden_layers=4,
                         num_attention_heads=8, num_key_value_heads=4, head_dim=128,
                         max_position_embeddings=4096),
@@ -209,6 +214,11 @@ class Qwen3Attention(nn.Module):
             o = flash_attention(q, k, v, B, S, self.hq, self.hkv, self.d, causal=True, kv_lens=kv_lens)
         elif isinstance(cache, PackedPrefill):
             o = cache.attend(self.layer_idx, q, k, v, self.hq, self.hkv, self.d, flash_attention)
+        elif cache.pos is not None and S == 1 and cache.fp8:
+            # decode over the FP8 cache: quantise + append + split-K attention on the codes, one kernel
+            o = decode_attention_append_fp8(q.reshape(B, -1), k.reshape(B, -1), v.reshape(B, -1), cache.k[self.layer_idx],
+                                            cache.v[self.layer_idx], cache.pos, self.hq, self.hkv, self.d,
+                                            max_len=cache.max_len)
         elif cache.pos is not None and S == 1:
             # decode: append at each row's own position, split-K attention over the cache
             o = decode_attention_append(q.reshape(B, -1), k.reshape(B, -1), v.reshape(B, -1), cache.k[self.layer_idx],
@@ -216,12 +226,18 @@ class Qwen3Attention(nn.Module):
                                         max_len=cache.max_len)
         else:
             kc, vc = cache.update(self.layer_idx, k.reshape(B, S, -1), v.reshape(B, S, -1), start)
+            if cache.fp8:
+                # the visible rows expanded to a bf16 transient of this layer.  The new rows are read back as well:
+                # a token has the same K/V bits in its own prefill, in a later chunk and after a prefix hit.
+                c, cv = cache.prefix_bf16(self.layer_idx, start + S)
+                k, v = c, cv
+            else:
+                c, cv = cache.k[self.layer_idx], cache.v[self.layer_idx]
             if start == 0:   # prefill: same fused kernel as training (causal + per-row key lengths)
                 o = flash_attention(q, k.reshape(B * S, -1), v.reshape(B * S, -1), B, S, self.hq, self.hkv, self.d,
                                     causal=True, kv_lens=kv_lens)
             else:   # chunked / suffix prefill: the new queries sit at start.. over the cache prefix
-                c = cache.k[self.layer_idx]
-                o = flash_attention_prefix(q, c, cache.v[self.layer_idx], B, S, start + S, self.hq, self.hkv,
+                o = flash_attention_prefix(q, c, cv, B, S, start + S, self.hq, self.hkv,
                                            self.d, q_offs=start, kv_lens=kv_lens, kv_rows=c.shape[1])
         if self.tp_group is None:
             return project([self.o_proj], o, residual, tr)

@@ -132,6 +132,8 @@ void launch_decode_attention_fp8(const void*, int, const void*, int, const void*
 void launch_kv_fp8_write_rows(const void*, long, const void*, long, void*, void*, const int64_t*, long, int, int, long,
                               hipStream_t);
 void launch_kv_fp8_dequant_rows(const void*, long, void*, long, int, int, hipStream_t);
+void launch_prefill_attention_fp8(const void*, long, const void*, const void*, const int*, const int*, const int*,
+                                  const int*, void*, int, int, int, int, int, int, int, int, float, hipStream_t);
 void launch_sample(int, const void*, const int*, int, float*, int64_t*, int, int, float, int, float, float, uint64_t,
                    hipStream_t);
 void launch_sample_logprobs(int, const void*, const int*, int, float*, int64_t*, float*, int64_t*, float*, int, int, int,
@@ -1925,6 +1927,38 @@ Tensor kv_fp8_dequant_rows(Tensor rows, int64_t hkv, int64_t d) {
   return out;
 }
 
+// Causal prefill attention over the codes: q [T, hq*d] bf16 (row-strided), caches uint8 [slots, Smax, hkv*(d+16)];
+// int32 descriptors cu_q [N+1], slots / q_offs [N], kv_lens [N] or None; the grid covers max_q queries per sequence
+Tensor prefill_attention_fp8(Tensor q, Tensor kc, Tensor vc, Tensor cu_q, Tensor slots, Tensor q_offs,
+                             optional<Tensor> kv_lens, int64_t max_q, int64_t hq, int64_t hkv, int64_t d, double scale) {
+  const char* who = "prefill_attention_fp8";
+  check_kv_fp8_dims(who, hkv, d);
+  TORCH_CHECK(hq % hkv == 0 && hq / hkv <= 16, who, ": group size hq / hkv <= 16");
+  TORCH_CHECK(q.dim() == 2, who, ": q is [T, hq*d]");
+  const int64_t T = q.size(0);
+  check_kv_fp8_rows(who, q, T, hq * d);
+  check_kv_fp8_cache(who, kc, hkv, d);
+  check_kv_fp8_cache(who, vc, hkv, d);
+  TORCH_CHECK(kc.dim() == 3 && vc.sizes() == kc.sizes(), who, ": caches are [slots, Smax, hkv*(d+16)]");
+  const int64_t N = slots.numel();
+  auto i32 = [&](const Tensor& t, int64_t n, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() == n, who, ": ", name,
+                " is int32 [", n, "] on the GPU, got ", t.scalar_type(), " [", t.numel(), "]");
+  };
+  i32(cu_q, N + 1, "cu_q");
+  i32(slots, N, "slots");
+  i32(q_offs, N, "q_offs");
+  if (kv_lens) i32(*kv_lens, N, "kv_lens");
+  TORCH_CHECK(max_q >= 0 && T <= 0x7fffffff && kc.size(0) * kc.size(1) <= 0x7fffffff, who, ": sizes beyond int32");
+  TORCH_CHECK(N <= 65535 && hq <= 65535, who, ": grid limits");
+  Tensor out = at::empty({T, hq * d}, q.options());   // rows outside cu_q / past max_q stay unwritten
+  launch_prefill_attention_fp8(q.data_ptr(), (long)q.stride(0), kc.data_ptr(), vc.data_ptr(), cu_q.data_ptr<int>(),
+                               slots.data_ptr<int>(), q_offs.data_ptr<int>(), kv_lens ? kv_lens->data_ptr<int>() : nullptr,
+                               out.data_ptr(), (int)T, (int)N, (int)max_q, (int)kc.size(0), (int)kc.size(1), (int)hq,
+                               (int)hkv, (int)d, (float)scale, stream());
+  return out;
+}
+
 // logits [B, V] fp32|bf16; hist [B, L] int32 (-1 = pad) or None; temperature <= 0 → greedy
 Tensor sample(Tensor logits, optional<Tensor> hist, double temperature, int64_t top_k, double top_p, double penalty,
               int64_t key) {
@@ -2236,6 +2270,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attention_append_fp8", &decode_attention_append_fp8);
   m.def("kv_fp8_write_rows", &kv_fp8_write_rows);
   m.def("kv_fp8_dequant_rows", &kv_fp8_dequant_rows);
+  m.def("prefill_attention_fp8", &prefill_attention_fp8);
   m.def("lora_proj", &lora_proj);
   m.def("lora_acc", &lora_acc);
   m.def("lora_proj2", &lora_proj2);

@@ -62,17 +62,6 @@ struct DropParams {
   float rinv;
 };
 
-// Grid (n0, n1, n2) → logical block (i0, i1, i2) with consecutive logical blocks (i0 fastest)
-// on the same XCD, so the blocks that re-read one (batch, kv-head)'s K/V (or Q/dO) share its L2.
-__device__ __forceinline__ void xcd_grid3(int& i0, int& i1, int& i2) {
-  const int n0 = gridDim.x, n1 = gridDim.y;
-  const int nwg = n0 * n1 * gridDim.z;
-  const int id = xcd_remap(blockIdx.x + n0 * (blockIdx.y + n1 * blockIdx.z), nwg);
-  i0 = id % n0;
-  i1 = (id / n0) % n1;
-  i2 = id / (n0 * n1);
-}
-
 // Causal grids (i0 = query block, work grows with it): the same XCD grouping, but inside each run of
 // n0·G consecutive logical blocks (G (head, batch) pairs — one XCD's share at the training shapes)
 // the block index varies SLOWEST, so every XCD dispatches all its heavy blocks before any light one

@@ -90,6 +90,17 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
 }
 
+// Grid (n0, n1, n2) → logical block (i0, i1, i2) with consecutive logical blocks (i0 fastest)
+// on the same XCD, so the blocks that re-read one (batch, kv-head)'s K/V (or Q/dO) share its L2.
+__device__ __forceinline__ void xcd_grid3(int& i0, int& i1, int& i2) {
+  const int n0 = gridDim.x, n1 = gridDim.y;
+  const int nwg = n0 * n1 * gridDim.z;
+  const int id = xcd_remap(blockIdx.x + n0 * (blockIdx.y + n1 * blockIdx.z), nwg);
+  i0 = id % n0;
+  i1 = (id / n0) % n1;
+  i2 = id / (n0 * n1);
+}
+
 // Counter-based dropout mask shared by every kernel that applies or regenerates the LoRA input
 // dropout (dropout.hip, lora.hip): 8 keep flags for elements [8v, 8v+8) of the row-major tensor,
 // a pure function of (key, v) — masks are never stored.

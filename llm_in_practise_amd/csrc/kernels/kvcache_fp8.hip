@@ -24,8 +24,21 @@
 //    Lengths come from pos (int64) on the device; the split count depends on (B, Hkv, max_len) alone.
 //  * kv_fp8_write_rows_k<D>: prefill K and V rows [T, Hkv·D] bf16 (row-strided) → head blocks at cache row idx[t];
 //    one lane per 16 elements, one 16-byte store per lane and one per tail.
-//  * kv_fp8_dequant_rows_k<D>: cache rows → bf16 [n, Hkv·D] = bf16(code · scale), for the prefix / chunked
-//    prefill path, which hands the transient to the bf16 prefix attention kernel.
+//  * kv_fp8_dequant_rows_k<D>: cache rows → bf16 [n, Hkv·D] = bf16(code · scale): the op behind kv_fp8_dequant_rows.  No
+//    serving path uses it since attn_prefill_fp8_k reads the codes; the benchmark's old path and the tests do.
+//  * attn_prefill_fp8_k<D>: causal GQA flash-attention forward for prefill, chunked prefill, prefix hits and packed
+//    admissions, reading the codes in place; grid (128-query block, q head, sequence) in xcd_grid3 order (the blocks
+//    and then the heads of a GQA group are neighbours on one XCD and share the codes in its L2), sequences described
+//    on the device by cu_q / slots / q_offs / kv_lens.  A 64-key tile is converted ONCE per workgroup: 16-byte
+//    global loads of the codes into registers one tile ahead of the MFMAs, cvt16 (exact), and a bf16 image in
+//    double-buffered LDS with D + 16 padded rows (the 16x16x32 K fragment reads ds_read_b128 and the transposed V
+//    reads ds_read_b64_tr_b16 are both conflict-free at that stride), which all four waves read; the tile's 128
+//    scales go through a small fp32 LDS array.  LDS-DMA moves bytes and cannot convert, so unlike attn_fwd128_k
+//    this kernel stages through registers.  Scores are swapped (Sᵀ = K·Qᵀ, a lane owns a query, lane-local fp32
+//    online softmax); as in the decode kernel the K scale multiplies the fp32 score with scale·log2(e) and the V
+//    scale multiplies P before P is rounded to bf16.  Tiles are aligned to key 0 and visited in ascending order,
+//    rows past the block's last visible row are never addressed, and skipped or masked tiles add exact zeros, so
+//    a query's output bits depend on its q row, its position and the cache rows it sees alone.
 #include "common.h"
 
 using namespace lipa;
@@ -382,7 +395,223 @@ __global__ __launch_bounds__(256) void kv_fp8_dequant_rows_k(const uint8_t* __re
   *reinterpret_cast<bf16x8*>(dst + 8) = o[1];
 }
 
+// ============================================================================ prefill attention over the codes
+// Sequence b of the launch owns query rows cu_q[b] .. cu_q[b+1]-1 of q / out and cache slot slots[b]; query i sits
+// at position q_offs[b] + i and sees rows j <= q_offs[b] + i (and j < kv_lens[b]) of its slot.  A workgroup is 128
+// queries of one q head (4 waves × 2 subtiles of 16); key tiles are 64 rows, aligned to row 0, ascending, up to
+// kend = the last row any query of the block sees: rows >= kend are never addressed (loads clamp to kend - 1, a
+// visible row, and the mask drops the duplicates).
+template <int D>
+__global__ __launch_bounds__(256, 2) void attn_prefill_fp8_k(const bf16* __restrict__ Q, long ldq,
+                                                             const uint8_t* __restrict__ kc,
+                                                             const uint8_t* __restrict__ vc,
+                                                             const int* __restrict__ cu_q, const int* __restrict__ slots,
+                                                             const int* __restrict__ q_offs,
+                                                             const int* __restrict__ kv_lens, bf16* __restrict__ O,
+                                                             int T, int nslots, int Smax, int hq, int hkv,
+                                                             float scale_log2) {
+  constexpr int HB = D + 16;        // bytes of a head block
+  constexpr int HL = D / 16;        // 16-code chunks of a head vector
+  constexpr int LDR = D + 16;       // padded LDS row (bf16 elements): conflict-free for both fragment reads
+  constexpr int TILE = 64 * LDR;    // elements of one K or V image
+  constexpr int NS = D / 32;        // K steps over the head dim
+  constexpr int ND = D / 16;        // d-subtiles of O
+  constexpr int LOADS = 64 * HL / 256;
+  constexpr int QT = 2, QB = 64 * QT;
+  __shared__ __attribute__((aligned(16))) bf16 smem[4 * TILE];      // K0 V0 K1 V1
+  __shared__ __attribute__((aligned(16))) float sscl[2][128];       // per buffer: 64 K scales, 64 V scales
+
+  int i0, h, b;
+  xcd_grid3(i0, h, b);
+  const int qb = gridDim.x - 1 - i0;   // heavy (late) blocks first
+  const int r0 = cu_q[b], Sq = cu_q[b + 1] - r0;
+  if (qb * QB >= Sq) return;           // uniform: no query of this workgroup exists (or an empty sequence)
+  const int slot = slots[b];
+  if (slot < 0 || slot >= nslots || r0 < 0 || r0 + Sq > T) return;   // descriptors outside q or the cache
+  const int hk = h / (hq / hkv);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
+  const int qoff = q_offs[b];
+  const int kvlen = min(kv_lens ? kv_lens[b] : Smax, Smax);
+  const int kend = min(qoff + min(qb * QB + QB, Sq), kvlen);   // rows the block's last query sees
+  const int nt = (kend + 63) / 64;
+  const int q0 = qb * QB + 16 * QT * w;
+  // last row any query of this wave sees; a wave with no query of its own computes nothing
+  const int wlim = q0 < Sq ? min(qoff + min(q0 + 16 * QT, Sq) - 1, kvlen - 1) : -1;
+
+  const size_t rs = (size_t)hkv * HB;
+  const uint8_t* kcb = kc + (size_t)slot * Smax * rs + hk * HB;
+  const uint8_t* vcb = vc + (size_t)slot * Smax * rs + hk * HB;
+
+  // Q fragments (B operand of Sᵀ = K·Qᵀ): Q[q0 + 16qt + li][32s + 8g + j]; rows past Sq repeat the last query
+  bf16x8 qf[QT][NS];
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) {
+    const int qi = min(q0 + 16 * qt + li, Sq - 1);
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+      qf[qt][s] = *reinterpret_cast<const bf16x8*>(Q + (size_t)(r0 + qi) * ldq + h * D + 32 * s + 8 * g);
+  }
+  f32x4 acc[ND][QT];
+  float m_run[QT], l_run[QT];
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) {
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt) acc[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    m_run[qt] = -INFINITY;
+    l_run[qt] = 0.f;
+  }
+
+  // a tile's codes (16 per load) and scales, in registers one tile ahead of the MFMAs
+  u32x4 kr[LOADS], vr[LOADS];
+  float scr = 0.f;
+  auto load_tile = [&](int t) {
+#pragma unroll
+    for (int p = 0; p < LOADS; ++p) {
+      const int ci = p * 256 + threadIdx.x;
+      const size_t off = (size_t)min(t * 64 + ci / HL, kend - 1) * rs + 16 * (ci % HL);
+      kr[p] = *reinterpret_cast<const u32x4*>(kcb + off);
+      vr[p] = *reinterpret_cast<const u32x4*>(vcb + off);
+    }
+    if (threadIdx.x < 128)
+      scr = *reinterpret_cast<const float*>((threadIdx.x < 64 ? kcb : vcb) + (size_t)min(t * 64 + lane, kend - 1) * rs + D);
+  };
+  // converted once for the four waves: codes → bf16 images (exact), scales → the fp32 array
+  auto store_tile = [&](int buf) {
+    bf16* Kl = smem + buf * 2 * TILE;
+    bf16* Vl = Kl + TILE;
+#pragma unroll
+    for (int p = 0; p < LOADS; ++p) {
+      const int ci = p * 256 + threadIdx.x;
+      const int o = (ci / HL) * LDR + 16 * (ci % HL);
+      bf16x8 a0, a1;
+      cvt16(kr[p], a0, a1);
+      *reinterpret_cast<bf16x8*>(Kl + o) = a0;
+      *reinterpret_cast<bf16x8*>(Kl + o + 8) = a1;
+      cvt16(vr[p], a0, a1);
+      *reinterpret_cast<bf16x8*>(Vl + o) = a0;
+      *reinterpret_cast<bf16x8*>(Vl + o + 8) = a1;
+    }
+    if (threadIdx.x < 128) sscl[buf][threadIdx.x] = scr;
+  };
+
+  if (nt > 0) load_tile(0);
+  for (int t = 0; t < nt; ++t) {
+    const int buf = t & 1;
+    store_tile(buf);
+    __syncthreads();   // one barrier per tile: buffer buf was last read two tiles ago, before the previous barrier
+    if (t + 1 < nt) load_tile(t + 1);
+    const int k0 = t * 64;
+    if (k0 > wlim) continue;   // wave-uniform: the tile lies above every query of this wave
+    const bf16* Kl = smem + buf * 2 * TILE;
+    const bf16* Vl = Kl + TILE;
+    // ---- Sᵀ[key][q] for 4 key subtiles × QT query subtiles
+    f32x4 sc[4][QT];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+      for (int qt = 0; qt < QT; ++qt) sc[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kl + (16 * kt + li) * LDR + 32 * s + 8 * g);
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt)
+          sc[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][s], sc[kt][qt], 0, 0, 0);
+      }
+    }
+    // the lane's keys are k0 + 16kt + 4g + r: their K scales (with scale·log2e) and V scales
+    f32x4 ks[4], sv[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      ks[kt] = *reinterpret_cast<const f32x4*>(&sscl[buf][16 * kt + 4 * g]) * scale_log2;
+      sv[kt] = *reinterpret_cast<const f32x4*>(&sscl[buf][64 + 16 * kt + 4 * g]);
+    }
+    // ---- mask + online softmax in the log2 domain (lane owns query q0 + 16qt + li)
+    bf16x8 pf[QT][2];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+      const int klim = min(qoff + min(q0 + 16 * qt + li, Sq - 1), kvlen - 1);   // last key this query sees
+      float mx = -INFINITY;
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = (k0 + 16 * kt + 4 * g + r <= klim) ? sc[kt][qt][r] * ks[kt][r] : -INFINITY;
+          sc[kt][qt][r] = v;
+          mx = fmaxf(mx, v);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float mn = fmaxf(m_run[qt], mx);
+      const bool dead = mn == -INFINITY;   // no key seen yet (only with kv_lens < 1)
+      const float alpha = dead ? 1.f : __builtin_amdgcn_exp2f(m_run[qt] - mn);
+      float rsum = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pr = dead ? 0.f : __builtin_amdgcn_exp2f(sc[kt][qt][r] - mn);
+          sc[kt][qt][r] = pr * sv[kt][r];   // the V scale rides on P; the sum keeps the plain p
+          rsum += pr;
+        }
+      rsum += __shfl_xor(rsum, 16, 64);
+      rsum += __shfl_xor(rsum, 32, 64);
+      l_run[qt] = l_run[qt] * alpha + rsum;
+      m_run[qt] = mn;
+#pragma unroll
+      for (int dt = 0; dt < ND; ++dt) acc[dt][qt] *= alpha;
+      // P as B operand, permuted key order j ↔ 32kb + 16(j>>2) + 4g + (j&3)
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+        pf[qt][kb] = bf16x8{(bf16)sc[2 * kb][qt][0], (bf16)sc[2 * kb][qt][1], (bf16)sc[2 * kb][qt][2],
+                            (bf16)sc[2 * kb][qt][3], (bf16)sc[2 * kb + 1][qt][0], (bf16)sc[2 * kb + 1][qt][1],
+                            (bf16)sc[2 * kb + 1][qt][2], (bf16)sc[2 * kb + 1][qt][3]};
+    }
+    // ---- Oᵀ[d][q] += Vᵀ[d][key] · Pᵀ[key][q]
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+      for (int dt = 0; dt < ND; ++dt) {
+        const bf16* p0 = Vl + (32 * kb + 4 * g + (li >> 2)) * LDR + 16 * dt + 4 * (li & 3);
+        const bf16x4 a = tr_read(p0), c = tr_read(p0 + 16 * LDR);
+        const bf16x8 vf = bf16x8{a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]};
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt)
+          acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qt][kb], acc[dt][qt], 0, 0, 0);
+      }
+    }
+  }
+  // ---- epilogue: O[q][16dt + 4g + r] = acc / l
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) {
+    const int qi = q0 + 16 * qt + li;
+    if (qi >= Sq) continue;
+    const float inv = l_run[qt] > 0.f ? 1.f / l_run[qt] : 0.f;
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt) {
+      bf16x4 o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = (bf16)(acc[dt][qt][r] * inv);
+      *reinterpret_cast<bf16x4*>(O + (size_t)(r0 + qi) * (hq * D) + h * D + 16 * dt + 4 * g) = o;
+    }
+  }
+}
+
 }  // namespace
+
+void launch_prefill_attention_fp8(const void* q, long ldq, const void* kc, const void* vc, const int* cu_q,
+                                  const int* slots, const int* q_offs, const int* kv_lens, void* out, int T, int N,
+                                  int max_q, int nslots, int Smax, int hq, int hkv, int d, float scale, hipStream_t st) {
+  if (N <= 0 || max_q <= 0) return;
+  dim3 grid((max_q + 127) / 128, hq, N);
+  const float sl2 = scale * 1.4426950408889634f;
+  if (d == 128)
+    attn_prefill_fp8_k<128><<<grid, 256, 0, st>>>((const bf16*)q, ldq, (const uint8_t*)kc, (const uint8_t*)vc, cu_q,
+                                                  slots, q_offs, kv_lens, (bf16*)out, T, nslots, Smax, hq, hkv, sl2);
+  else
+    attn_prefill_fp8_k<64><<<grid, 256, 0, st>>>((const bf16*)q, ldq, (const uint8_t*)kc, (const uint8_t*)vc, cu_q,
+                                                 slots, q_offs, kv_lens, (bf16*)out, T, nslots, Smax, hq, hkv, sl2);
+  LIPA_CHECK_LAUNCH();
+}
 
 int decode_fp8_split_plan(int B, int hkv, int max_len) { return decode_split_plan2(B, hkv, max_len); }
 

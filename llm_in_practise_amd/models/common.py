@@ -6,8 +6,10 @@ import dataclasses
 import torch
 import torch.nn as nn
 
+from ..ops._native import use_native
 from ..ops.attention import flash_attention_varlen, native_ok
-from ..ops.kv_fp8 import HEAD_DIMS as FP8_KV_HEAD_DIMS, kv_fp8_dequant_rows, kv_fp8_write_rows, row_bytes
+from ..ops.kv_fp8 import (HEAD_DIMS as FP8_KV_HEAD_DIMS, kv_fp8_dequant_rows, kv_fp8_write_rows, prefill_attention_fp8,
+                          row_bytes)
 from ..ops.linear import LoraBranch, fused_linear
 from ..peft.lora import Linear4bit, LoraLayer, base_of
 from ..quant.fp8 import Fp8Linear, Fp8Weight, fp8_linear
@@ -240,6 +242,8 @@ class PackedPrefill:
         self.last = (torch.cumsum(torch.tensor(lens), 0) - 1).to(device)
         self.cu_host = [0] + torch.cumsum(torch.tensor(lens), 0).tolist()
         self.cu_seqlens = torch.tensor(self.cu_host, dtype=torch.int32, device=device)
+        self.slots = torch.tensor(slots, dtype=torch.int32, device=device)      # FP8 cache: the prompts' descriptors
+        self.q_offs = torch.zeros(len(lens), dtype=torch.int32, device=device)
 
     def attend(self, layer: int, q, k, v, hq: int, hkv: int, d: int, attention_fn):
         if self.cache.fp8:
@@ -247,6 +251,8 @@ class PackedPrefill:
             # later chunk or a prefix hit will see
             ck, cv = self.cache.k[layer], self.cache.v[layer]
             kv_fp8_write_rows(k, v, ck, cv, self.cache_idx, hkv, d)
+            if use_native(q):   # one launch over the codes in the slots, no gathered or dequantised copy
+                return prefill_attention_fp8(q, ck, cv, self.cu_seqlens, self.slots, self.q_offs, self.S, hq, hkv, d)
             k = kv_fp8_dequant_rows(ck.view(-1, ck.shape[-1]).index_select(0, self.cache_idx), hkv, d)
             v = kv_fp8_dequant_rows(cv.view(-1, cv.shape[-1]).index_select(0, self.cache_idx), hkv, d)
         else:
@@ -275,7 +281,8 @@ class KVCache:
 
     ``kv_dtype="fp8"``: rows are ``uint8 [Hkv*(D+16)]`` — per head D e4m3 codes and a 16-byte tail that starts
     with the fp32 scale (``ops/kv_fp8.py``), 0.5625 of the bf16 bytes at D = 128.  Writes quantise; the decode
-    step runs ``decode_attention_append_fp8`` on the codes; a prefix read dequantises the rows it needs."""
+    step runs ``decode_attention_append_fp8`` and every prefill ``prefill_attention_fp8`` on the codes; the torch
+    reference path dequantises the rows a prefix read needs (``prefix_bf16``)."""
 
     def __init__(self, n_layers: int, batch: int, max_len: int, hkv: int, d: int, dtype, device,
                  kv_dtype: str | None = None):
@@ -313,6 +320,17 @@ class KVCache:
             return
         self.k[layer][self._rows, self.pos] = k
         self.v[layer][self._rows, self.pos] = v
+
+    def prefill_desc(self, B: int, S: int, start: int):
+        """The int32 descriptors ``(cu_q, slots, q_offs)`` of ``prefill_attention_fp8`` for a rectangular ``[B, S]``
+        prefill at ``start`` into slots ``0..B-1``, built once per prefill call and shared by the layers."""
+        if getattr(self, "_desc_key", None) != (B, S, start):
+            dev = self._rows.device
+            self._desc = (torch.arange(B + 1, dtype=torch.int32, device=dev) * S,
+                          torch.arange(B, dtype=torch.int32, device=dev),
+                          torch.full((B,), start, dtype=torch.int32, device=dev))
+            self._desc_key = (B, S, start)
+        return self._desc
 
     def prefix_bf16(self, layer: int, n: int):
         """FP8 cache: the first ``n`` rows of every slot of this (view of the) cache expanded to bf16

@@ -25,11 +25,12 @@ import torch
 import torch.nn as nn
 
 from ..ops import reference as ref
+from ..ops._native import use_native
 from ..ops.activation import swiglu_fused
 from ..ops.mlp import fusable as mlp_fusable, swiglu_mlp
 from ..ops.attention import check_cu_seqlens, flash_attention, flash_attention_prefix, flash_attention_varlen
 from ..ops.decode import decode_attention_append
-from ..ops.kv_fp8 import decode_attention_append_fp8
+from ..ops.kv_fp8 import decode_attention_append_fp8, prefill_attention_fp8
 from ..ops.linear import checkpoint as lora_checkpoint
 from ..ops.loss import fused_linear_cross_entropy, shift_labels
 from ..ops.norm import RMSNorm, rms_norm, rms_norm_residual
@@ -224,11 +225,18 @@ class Qwen3Attention(nn.Module):
             o = decode_attention_append(q.reshape(B, -1), k.reshape(B, -1), v.reshape(B, -1), cache.k[self.layer_idx],
                                         cache.v[self.layer_idx], cache.pos, self.hq, self.hkv, self.d,
                                         max_len=cache.max_len)
+        elif cache.fp8 and use_native(q):
+            # prefill, a chunk or the suffix after a prefix hit over the FP8 cache: the new rows are quantised into the
+            # slots and read back as codes together with every earlier row by one kernel, so a token has the same K/V
+            # bits in its own prefill, in a later chunk, after a prefix hit and in every decode step
+            cache.update(self.layer_idx, k.reshape(B, S, -1), v.reshape(B, S, -1), start)
+            cu, slots, offs = cache.prefill_desc(B, S, start)
+            o = prefill_attention_fp8(q, cache.k[self.layer_idx], cache.v[self.layer_idx], cu, slots, offs, S, self.hq,
+                                      self.hkv, self.d, kv_lens=kv_lens)
         else:
             kc, vc = cache.update(self.layer_idx, k.reshape(B, S, -1), v.reshape(B, S, -1), start)
             if cache.fp8:
-                # the visible rows expanded to a bf16 transient of this layer.  The new rows are read back as well:
-                # a token has the same K/V bits in its own prefill, in a later chunk and after a prefix hit.
+                # reference path: the visible rows expanded to a bf16 transient of this layer, new rows included
                 c, cv = cache.prefix_bf16(self.layer_idx, start + S)
                 k, v = c, cv
             else:

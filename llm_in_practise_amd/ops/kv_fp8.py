@@ -117,3 +117,44 @@ def decode_attention_append_fp8(q, k, v, kc, vc, pos, hq, hkv, d, max_len=None, 
                                                     _rows16(v.to(torch.bfloat16)), kc, vc, pos.contiguous(), hq, hkv,
                                                     d, int(max_len or kc.shape[1]), float(scale))
     return decode_attention_append_fp8_reference(q, k, v, kc, vc, pos, hq, hkv, d, scale)
+
+
+def prefill_attention_fp8_reference(q, kc, vc, cu_q, slots, q_offs, max_q, hq, hkv, d, kv_lens=None, scale=None,
+                                    dtype=torch.float32):
+    """The specification of :func:`prefill_attention_fp8`: per sequence, softmax attention in ``dtype`` over
+    ``codes.float() · scale`` of the rows its queries may see.  No other cache row is touched.
+    ``dtype=torch.float64`` is the tests' oracle (returned as fp64); the fp32 default returns ``q``'s dtype."""
+    Smax, G = kc.shape[1], hq // hkv
+    scale = scale if scale is not None else 1.0 / math.sqrt(d)
+    out = torch.zeros(q.shape[0], hq * d, dtype=dtype, device=q.device)
+    cu, sl, qo = cu_q.tolist(), slots.tolist(), q_offs.tolist()
+    kl = kv_lens.tolist() if kv_lens is not None else [Smax] * len(sl)
+    for b, (r0, r1) in enumerate(zip(cu, cu[1:])):
+        n = min(r1 - r0, max_q)
+        vis = min(qo[b] + n, kl[b], Smax)
+        if n <= 0 or vis <= 0:
+            continue
+        kf, vf = (kv_fp8_dequant_rows_reference(c[sl[b], :vis], hkv, d, dtype).view(vis, hkv, d) for c in (kc, vc))
+        s = torch.einsum("nhgd,shd->hgns", q[r0:r0 + n].to(dtype).view(n, hkv, G, d), kf) * scale
+        seen = torch.arange(vis, device=q.device)[None, :] <= (qo[b] + torch.arange(n, device=q.device))[:, None]
+        p = torch.softmax(s.masked_fill(~seen, float("-inf")), -1)
+        out[r0:r0 + n] = torch.einsum("hgns,shd->nhgd", p, vf).reshape(n, hq * d)
+    return out if dtype == torch.float64 else out.to(q.dtype)
+
+
+def prefill_attention_fp8(q, kc, vc, cu_q, slots, q_offs, max_q, hq, hkv, d, kv_lens=None, scale=None):
+    """Causal GQA attention of new queries over an FP8 cache that already holds their K/V rows
+    (:func:`kv_fp8_write_rows` first, same stream): prefill, chunked prefill, prefix hits and packed admissions.
+
+    ``q`` ``[T, hq*d]`` bf16 (a row-strided view of the fused q|k|v output is taken as it is, see ``_rows16``);
+    ``kc`` / ``vc`` ``uint8 [slots, Smax, hkv*(d+16)]``.  Sequence ``b`` of ``N`` owns query rows
+    ``cu_q[b] .. cu_q[b+1]-1`` (int32 ``[N+1]``; at most ``max_q`` each; empty sequences are legal) and cache slot
+    ``slots[b]`` (int32 ``[N]``, as ``q_offs`` and ``kv_lens``); query ``i`` sits at position ``q_offs[b] + i`` and
+    sees rows ``j <= q_offs[b] + i`` of its slot, and ``j < kv_lens[b]`` (each >= 1) where given.  All descriptors
+    stay on the device.  Returns ``[T, hq*d]``; rows no sequence owns are undefined.  On gfx950 this is one launch of ``attn_prefill_fp8_k`` on the codes."""
+    _check(hq, hkv, d, kc, vc)
+    scale = scale if scale is not None else 1.0 / math.sqrt(d)
+    if use_native(q):   # the binding checks the descriptors: int32, contiguous, [N+1] / [N]
+        return native().prefill_attention_fp8(_rows16(q.to(torch.bfloat16)), kc, vc, cu_q, slots, q_offs, kv_lens,
+                                              int(max_q), hq, hkv, d, float(scale))
+    return prefill_attention_fp8_reference(q, kc, vc, cu_q, slots, q_offs, max_q, hq, hkv, d, kv_lens, scale)

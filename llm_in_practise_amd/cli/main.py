@@ -272,9 +272,33 @@ def _parallel(a=None):
     return dist.group.WORLD, tp_group, pp_group
 
 
+def _is_moe(path: str) -> bool:
+    """``random:<preset>`` or an HF directory that describes a Qwen3-MoE model."""
+    from ..models.qwen3 import PRESETS
+    if path.startswith("random:"):
+        return PRESETS.get(path[7:], {}).get("num_experts", 0) > 0
+    cfgp = os.path.join(path, "config.json")
+    if not os.path.exists(cfgp):
+        return False
+    with open(cfgp) as f:
+        d = json.load(f)
+    return d.get("model_type") == "qwen3_moe" or (d.get("num_experts") or d.get("num_local_experts") or 0) > 0
+
+
 def _load_for_inference(path, adapter=None, device=None, quant=None, fuse=True, tp_group=None, pp_group=None):
     from ..models.qwen3 import BitsAndBytesConfig, Qwen3ForCausalLM, qwen3_config
     dev = device or _device()
+    if _is_moe(path):       # Qwen3-MoE: one GPU, bf16 experts, attention-only adapters; refused before anything loads
+        from ..infer.engine import check_moe_serving
+        stored = None
+        if not path.startswith("random:"):
+            with open(os.path.join(path, "config.json")) as f:
+                stored = (json.load(f).get("quantization_config") or {}).get("quant_method")
+        try:
+            check_moe_serving(tp=1 if tp_group is None else 2, pp=1 if pp_group is None else 2,
+                              quant=quant or stored, adapters=[adapter] if adapter else [])
+        except ValueError as e:
+            raise SystemExit(str(e))
     if quant == "fp8" and (tp_group is not None or pp_group is not None):
         raise SystemExit(_FP8_NO_TP)
     if tp_group is not None or pp_group is not None:   # shard the bf16 weights (+ adapter), THEN quantise

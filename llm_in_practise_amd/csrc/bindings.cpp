@@ -100,6 +100,9 @@ void launch_moe_permute(const int*, int, int, int*, int*, int*, hipStream_t);
 void launch_moe_gather(int, const void*, const int*, const float*, void*, int, int, int, hipStream_t);
 void launch_moe_combine(int, const void*, const int*, const float*, const void*, void*, int, int, int, hipStream_t);
 void launch_moe_wgrad(int, const void*, const void*, const int*, float*, int, int, int, hipStream_t);
+int moe_gemm_class(int, int);
+void launch_moe_gemm(int, int, const void*, const int*, int, const int*, const void*, void*, int, int, int, int,
+                     hipStream_t);
 int lora_acc_chunks(int M, int K);
 void launch_lora_proj2(const void*, int, const void*, const void*, int, int, int, float*, int, void*, int, int, uint64_t, float, float,
                        uint64_t, float, float, size_t, uint8_t*, float*, hipStream_t);
@@ -2122,8 +2125,9 @@ std::vector<Tensor> sample_rows(Tensor logits, Tensor temperature, Tensor top_k,
 // ---- MoE routing / dispatch (moe.hip)
 std::vector<Tensor> moe_route(Tensor logits, int64_t k, int64_t mode, bool want_probs) {
   CHECK_CONTIG(logits);
-  TORCH_CHECK(logits.dim() == 2 && logits.size(1) <= 64 && k >= 1 && k <= 8 && k <= logits.size(1),
-              "moe_route: logits [T, E<=64], 1<=k<=min(8,E)");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) <= 128 && k >= 1 && k <= 8 && k <= logits.size(1),
+              "moe_route: logits [T, E<=128], 1<=k<=min(8,E)");
+  TORCH_CHECK(logits.size(1) <= 64 || !want_probs, "moe_route: 64 < E <= 128 is forward only (no probs)");
   const int T = logits.size(0), E = logits.size(1);
   auto oi = logits.options();
   Tensor idx = torch::empty({T, k}, oi.dtype(at::kInt));
@@ -2193,6 +2197,53 @@ Tensor moe_wgrad(Tensor dout, Tensor ys, Tensor pos_of, int64_t k) {
   return dw;
 }
 
+// ---- grouped expert GEMMs (moe_gemm.hip).  row_class: 0 = from (P, E), 1 = skinny, 2 = tiled (tests force one)
+namespace {
+int moe_gemm_pick(int64_t row_class, int P, int E) {
+  TORCH_CHECK(row_class >= 0 && row_class <= 2, "moe_gemm: row_class 0 (auto), 1 (skinny) or 2 (tiled)");
+  return row_class ? (int)row_class : moe_gemm_class(P, E);
+}
+void moe_gemm_check(const char* who, const Tensor& a, const Tensor& offsets, const Tensor& w, int64_t H, int64_t I) {
+  TORCH_CHECK(a.is_cuda() && w.is_cuda() && offsets.is_cuda(), who, ": device tensors");
+  TORCH_CHECK(a.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, who, ": bf16 operands");
+  TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.dim() == 1 && offsets.is_contiguous(), who,
+              ": offsets int32 [E+1]");
+  TORCH_CHECK(w.dim() == 3 && w.size(0) == offsets.numel() - 1 && w.size(0) >= 1 && w.size(0) <= 128, who,
+              ": 1 <= E <= 128 experts, offsets [E+1]");
+  TORCH_CHECK(H % 64 == 0 && I % 32 == 0 && H > 0 && I > 0, who, ": H % 64 == 0 and I % 32 == 0");
+}
+}  // namespace
+
+Tensor moe_gemm_swiglu(Tensor x, Tensor perm, Tensor offsets, Tensor w13, int64_t k, int64_t row_class) {
+  CHECK_CONTIG(x); CHECK_CONTIG(perm); CHECK_CONTIG(w13);
+  TORCH_CHECK(x.dim() == 2 && w13.dim() == 3 && w13.size(2) == x.size(1) && w13.size(1) % 2 == 0,
+              "moe_gemm_swiglu: x [T, H], w13 [E, 2I, H]");
+  const int64_t H = x.size(1), I = w13.size(1) / 2;
+  moe_gemm_check("moe_gemm_swiglu", x, offsets, w13, H, I);
+  TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == at::kInt && k >= 1 && perm.numel() == x.size(0) * k &&
+              perm.numel() < (1 << 24), "moe_gemm_swiglu: perm int32 [T*k]");
+  const int P = perm.numel(), E = w13.size(0);
+  Tensor hs = torch::empty({P, I}, x.options());
+  if (P) launch_moe_gemm(0, moe_gemm_pick(row_class, P, E), x.data_ptr(), perm.data_ptr<int>(), (int)k,
+                         offsets.data_ptr<int>(), w13.data_ptr(), hs.data_ptr(), P, E, (int)I, (int)H, stream());
+  return hs;
+}
+
+Tensor moe_gemm_down(Tensor hs, Tensor offsets, Tensor w2, int64_t row_class) {
+  CHECK_CONTIG(hs); CHECK_CONTIG(w2);
+  TORCH_CHECK(hs.dim() == 2 && w2.dim() == 3 && w2.size(2) == hs.size(1), "moe_gemm_down: hs [P, I], w2 [E, H, I]");
+  const int64_t H = w2.size(1), I = hs.size(1);
+  moe_gemm_check("moe_gemm_down", hs, offsets, w2, H, I);
+  TORCH_CHECK(hs.size(0) < (1 << 24), "moe_gemm_down: < 2^24 rows");
+  const int P = hs.size(0), E = w2.size(0);
+  Tensor ys = torch::empty({P, H}, hs.options());
+  if (P) launch_moe_gemm(1, moe_gemm_pick(row_class, P, E), hs.data_ptr(), nullptr, 1, offsets.data_ptr<int>(),
+                         w2.data_ptr(), ys.data_ptr(), P, E, (int)H, (int)I, stream());
+  return ys;
+}
+
+int64_t moe_gemm_class_py(int64_t P, int64_t E) { return moe_gemm_class((int)P, (int)E); }
+
 // ------------------------------------------------------------------ custom all-reduce (allreduce.hip)
 int64_t car_alloc_py(int64_t bytes, bool uncached) {
   void* p = car_alloc((size_t)bytes, uncached);
@@ -2249,6 +2300,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gather", &moe_gather);
   m.def("moe_combine", &moe_combine);
   m.def("moe_wgrad", &moe_wgrad);
+  m.def("moe_gemm_swiglu", &moe_gemm_swiglu, py::arg("x"), py::arg("perm"), py::arg("offsets"), py::arg("w13"),
+        py::arg("k"), py::arg("row_class") = 0);
+  m.def("moe_gemm_down", &moe_gemm_down, py::arg("hs"), py::arg("offsets"), py::arg("w2"), py::arg("row_class") = 0);
+  m.def("moe_gemm_class", &moe_gemm_class_py);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd", &layernorm_bwd);

@@ -36,7 +36,7 @@ EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX")
 # for kernels added from this file on, so that their fp32 epilogues and fixed-order sums compile to the scalar
 # instructions the source spells out.  Per lane the result is the same IEEE operation.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-_EXTRA_KFLAGS = {"fp8.hip": _NO_PK_F32, "kvcache_fp8.hip": _NO_PK_F32}
+_EXTRA_KFLAGS = {"fp8.hip": _NO_PK_F32, "kvcache_fp8.hip": _NO_PK_F32, "moe_gemm.hip": _NO_PK_F32}
 
 
 def _torch_flags():

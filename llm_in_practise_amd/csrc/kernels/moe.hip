@@ -9,7 +9,8 @@
 //  * moe_route:   one wave per token, one lane per expert (E <= 64): top-k by k rounds of
 //                 wave arg-max (DPP/shuffle reductions), softmax over the k winners (or the
 //                 full softmax first: "softmax_topk"), plus the full router softmax for the
-//                 load-balance loss.  The backward is the same shape.
+//                 load-balance loss.  The backward is the same shape.  64 < E <= 128 (Qwen3-MoE: 128
+//                 experts, top-8) runs a forward-only variant with two experts per lane.
 //  * moe_permute: one workgroup per expert streams the T·k expert ids: a ballot/popcount pass
 //                 counts the ids below e (→ segment offset) and a second pass gives every
 //                 pair routed to e its STABLE rank (token order) → pos_of[pair], perm[row],
@@ -59,6 +60,51 @@ __global__ __launch_bounds__(256) void moe_route_k(const T* __restrict__ logits,
     sel[j] = v;
     sid[j] = i;
     if (lane == i) cur = -INFINITY;
+  }
+  if (lane < K) {
+    float val = 0.f;
+    int id = 0;
+    float m0 = sel[0], s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j >= K) continue;
+      if (j == lane) { val = sel[j]; id = sid[j]; }
+      s += __expf(sel[j] - m0);
+    }
+    idx[(size_t)t * K + lane] = id;
+    w[(size_t)t * K + lane] = mode == 0 ? __expf(val - m0) / s : val;
+  }
+}
+
+// 64 < E <= 128, forward only: lane l holds experts l and l + 64.  A round takes the better of the lane's two
+// (the lower id on a tie, as wave_argmax does across lanes), then the wave arg-max.  logits [T, E] as above.
+template <typename T>
+__global__ __launch_bounds__(256) void moe_route2_k(const T* __restrict__ logits, int* __restrict__ idx,
+                                                    float* __restrict__ w, int Ntok, int E, int K, int mode) {
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (t >= Ntok) return;
+  const bool has1 = lane + 64 < E;
+  const float x0 = to_f(logits[(size_t)t * E + lane]);
+  const float x1 = has1 ? to_f(logits[(size_t)t * E + lane + 64]) : -INFINITY;
+  const float mx = wave_max(fmaxf(x0, x1));
+  const float e0 = __expf(x0 - mx), e1 = has1 ? __expf(x1 - mx) : 0.f;
+  const float den = wave_sum(e0 + e1);
+  float c0 = mode == 0 ? x0 : e0 / den;
+  float c1 = !has1 ? -INFINITY : (mode == 0 ? x1 : e1 / den);
+  float sel[8];
+  int sid[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    sel[j] = -INFINITY;
+    sid[j] = 0;
+    if (j >= K) continue;
+    float v = c1 > c0 ? c1 : c0;
+    int i = c1 > c0 ? lane + 64 : lane;
+    wave_argmax(v, i);
+    sel[j] = v;
+    sid[j] = i;
+    if (i == lane) c0 = -INFINITY;
+    if (i == lane + 64) c1 = -INFINITY;
   }
   if (lane < K) {
     float val = 0.f;
@@ -234,6 +280,13 @@ inline int grid_for(size_t n) {
 void launch_moe_route(int dtype, const void* logits, int* idx, float* w, float* probs, int Ntok, int E, int K, int mode,
                       hipStream_t st) {
   const int g = (Ntok + 3) / 4;
+  if (E > 64) {          // forward only (no probs): the binding checks
+    if (dtype == 1)
+      moe_route2_k<bf16><<<g, 256, 0, st>>>((const bf16*)logits, idx, w, Ntok, E, K, mode);
+    else
+      moe_route2_k<float><<<g, 256, 0, st>>>((const float*)logits, idx, w, Ntok, E, K, mode);
+    return;
+  }
   if (dtype == 1)
     moe_route_k<bf16><<<g, 256, 0, st>>>((const bf16*)logits, idx, w, probs, Ntok, E, K, mode);
   else

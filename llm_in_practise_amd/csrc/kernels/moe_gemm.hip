@@ -1,0 +1,303 @@
+// Grouped expert GEMMs for routed MoE blocks on gfx950 (Qwen3-MoE serving).
+//
+// moe.hip sorts the T·k (token, expert) pairs into contiguous per-expert segments (perm, offsets).  The two
+// kernels here run the expert MLP over all segments in one launch each, with nothing read back to the host:
+//
+//   stage 0 (swiglu): hs[p, n] = bf16(silu(g) · u),  g = x[perm[p]/k] · w13[e, n]ᵀ,  u = x[perm[p]/k] · w13[e, I + n]ᵀ
+//   stage 1 (down):   ys[p, n] = bf16(hs[p] · w2[e, n]ᵀ)
+//
+// for p in [offsets[e], offsets[e+1]).  The gather of x is folded into the operand addressing (no xs copy) and
+// SwiGLU runs on the fp32 accumulators, so a workgroup always holds the gate and the up rows of the same
+// output columns.  Both kernels accumulate a pair's K loop in ascending 32-wide MFMA steps into one
+// accumulator (v_mfma_f32_16x16x32_bf16, W fragment = A operand, activation rows = B operand), so an output
+// row depends only on its own input row and its expert's weights: not on the rows it shares a tile with, its
+// place in the segment, or P.  No atomics, no split-K.
+//
+// Two row classes, picked on the host from (P, E) alone (moe_gemm_class) so that a captured graph is valid
+// for every routing:
+//
+//  * skinny (decode: a handful of rows per expert; the cost is streaming each live expert's weights once).
+//    Grid E × ceil(N/128): blockIdx gives (expert, weight-row block) directly and a workgroup whose expert
+//    has no rows returns at once.  As in skinny.hip a wave's two 16-row W fragments come straight from HBM
+//    with 16-byte loads, eight k-steps in flight; the expert's rows are the B operands of up to four 16-row
+//    m-tiles (1, 2 or 4 by the segment's size, a wave-uniform branch on the device).  Longer segments loop
+//    over groups of 64 rows and re-read W from L2.
+//  * tiled (prefill: tens to hundreds of rows per expert).  64-row × 128-weight-row tiles, BK = 64.  The grid
+//    is (min(P, P/64 + E) row tiles) × ceil(N/128); every wave scans ceil(c_e/64) over the E <= 128 experts
+//    (two per lane, shuffle prefix sum) to find its (expert, row tile); tiles past the total return at once.
+//    W and the gathered activation rows go global → LDS by LDS-DMA (global_load_lds_dwordx4, per-lane global
+//    addresses, so the gather costs nothing), double buffered.  The DMA writes lane l of a wave to slot l of
+//    a 1-KiB run, so the XOR swizzle that keeps the 16-row fragment reads off the same banks is applied on
+//    the global side: slot s of row r holds 16-B chunk s ^ (r & 7).  Ragged last row tiles and ragged N
+//    blocks are clamped on load and masked on store, never padded in memory.
+#include "common.h"
+
+using namespace lipa;
+
+namespace {
+
+constexpr int MG_KS = 8;      // skinny: k-steps (of 32) per load batch
+constexpr int MG_BM = 64;     // tiled: rows per tile
+constexpr int MG_BN = 128;    // weight rows per workgroup (both classes); swiglu: 64 gate + 64 up
+constexpr int MG_BK = 64;     // tiled: K per LDS stage
+
+__device__ __forceinline__ float silu_mul(float g, float u) { return g / (1.f + __expf(-g)) * u; }
+
+__device__ __forceinline__ void store4(bf16* p, float a, float b, float c, float d) {
+  bf16x4 o;
+  o[0] = (bf16)a; o[1] = (bf16)b; o[2] = (bf16)c; o[3] = (bf16)d;
+  *reinterpret_cast<bf16x4*>(p) = o;
+}
+
+// Epilogue shared by both classes.  acc[j] holds C[n = nrow[j] + 4g + i][row]; SWIGLU: j = 0 gate, j = 1 up of
+// the same logical columns → one 8-byte store; DOWN: one 8-byte store per fragment.
+template <bool SWIGLU>
+__device__ __forceinline__ void store_pair(bf16* out, int ldo, int p, int col0, int col1, const f32x4& a0,
+                                           const f32x4& a1) {
+  bf16* o = out + (size_t)p * ldo;
+  if (SWIGLU) {
+    store4(o + col0, silu_mul(a0[0], a1[0]), silu_mul(a0[1], a1[1]), silu_mul(a0[2], a1[2]), silu_mul(a0[3], a1[3]));
+  } else {
+    store4(o + col0, a0[0], a0[1], a0[2], a0[3]);
+    store4(o + col1, a1[0], a1[1], a1[2], a1[3]);
+  }
+}
+
+// ------------------------------------------------------------------ skinny
+// One group of up to 16·MT rows [r0, r1) of the segment against this wave's two W fragments.
+template <bool SWIGLU, int MT>
+__device__ __forceinline__ void skinny_rows(const bf16* __restrict__ A, const int* __restrict__ perm, int kdiv,
+                                            const bf16* wr0, const bf16* wr1, bf16* __restrict__ out, int ldo, int K,
+                                            int r0, int r1, int col0, int col1) {
+  const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+  const bf16* xr[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int p = min(r0 + 16 * mt + li, r1 - 1);
+    xr[mt] = A + (size_t)(perm ? perm[p] / kdiv : p) * K + 8 * g;
+  }
+  f32x4 acc[2][MT];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kb = 0; kb < K; kb += 32 * MG_KS) {
+    const int ns = min(MG_KS, (K - kb) / 32);
+    bf16x8 a0[MG_KS], a1[MG_KS];
+#pragma unroll
+    for (int s = 0; s < MG_KS; ++s)
+      if (s < ns) {
+        a0[s] = *reinterpret_cast<const bf16x8*>(wr0 + kb + 32 * s);
+        a1[s] = *reinterpret_cast<const bf16x8*>(wr1 + kb + 32 * s);
+      }
+#pragma unroll
+    for (int s = 0; s < MG_KS; ++s)
+      if (s < ns) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          const bf16x8 b = *reinterpret_cast<const bf16x8*>(xr[mt] + kb + 32 * s);
+          acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[s], b, acc[0][mt], 0, 0, 0);
+          acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[s], b, acc[1][mt], 0, 0, 0);
+        }
+      }
+  }
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int p = r0 + 16 * mt + li;
+    if (p < r1) store_pair<SWIGLU>(out, ldo, p, col0 + 4 * g, col1 + 4 * g, acc[0][mt], acc[1][mt]);
+  }
+}
+
+// A [rows, K] (x through perm for SWIGLU, hs for DOWN); W [E, NW, K] with NW = 2N (SWIGLU) or N (DOWN);
+// out [P, N].  grid = E · ceil(N / (SWIGLU ? 64 : 128)).
+template <bool SWIGLU>
+__global__ __launch_bounds__(256) void moe_gemm_skinny_k(const bf16* __restrict__ A, const int* __restrict__ perm,
+                                                         int kdiv, const int* __restrict__ offsets,
+                                                         const bf16* __restrict__ W, bf16* __restrict__ out, int N,
+                                                         int K, int nblk) {
+  const int e = blockIdx.x / nblk, bn = blockIdx.x % nblk;
+  const int s0 = offsets[e], s1 = offsets[e + 1];
+  if (s1 <= s0) return;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+  // SWIGLU: 16 logical columns per wave (fragment 0 = gate rows, 1 = up rows); DOWN: 32 columns per wave
+  const int col0 = SWIGLU ? bn * 64 + 16 * w : bn * 128 + 32 * w;
+  const int col1 = SWIGLU ? col0 : col0 + 16;
+  if (col0 >= N) return;                    // N % 32 == 0 (SWIGLU: % 16): a wave is wholly in or out
+  const bf16* We = W + (size_t)e * (SWIGLU ? 2 : 1) * N * K;
+  const bf16* wr0 = We + (size_t)(col0 + li) * K + 8 * g;
+  const bf16* wr1 = We + (size_t)((SWIGLU ? N + col0 : col1) + li) * K + 8 * g;
+  for (int r0 = s0; r0 < s1; r0 += 64) {
+    const int r1 = min(s1, r0 + 64), n = r1 - r0;
+    if (n <= 16) skinny_rows<SWIGLU, 1>(A, perm, kdiv, wr0, wr1, out, N, K, r0, r1, col0, col1);
+    else if (n <= 32) skinny_rows<SWIGLU, 2>(A, perm, kdiv, wr0, wr1, out, N, K, r0, r1, col0, col1);
+    else skinny_rows<SWIGLU, 4>(A, perm, kdiv, wr0, wr1, out, N, K, r0, r1, col0, col1);
+  }
+}
+
+// ------------------------------------------------------------------ tiled
+typedef __attribute__((address_space(3))) void* lds_ptr;
+typedef const __attribute__((address_space(1))) void* glb_ptr;
+
+// 16 bytes per lane, global → LDS: lane l lands at lds + 16·l (lds is wave-uniform)
+__device__ __forceinline__ void dma16(const bf16* gsrc, bf16* lds) {
+  __builtin_amdgcn_global_load_lds((glb_ptr)gsrc, (lds_ptr)lds, 16, 0, 0);
+}
+
+// Tile t of the launch → (expert, first row, segment end); false when t is past the last tile.  Each lane
+// holds experts 2l and 2l+1; an inclusive shuffle scan of their tile counts orders the tiles by expert.
+__device__ __forceinline__ bool find_tile(const int* __restrict__ offsets, int E, int t, int& e, int& r0, int& s1) {
+  const int lane = threadIdx.x & 63;
+  const int ea = 2 * lane, eb = ea + 1;
+  const int o0 = offsets[min(ea, E)], o1 = offsets[min(eb, E)], o2 = offsets[min(eb + 1, E)];
+  const int ca = (o1 - o0 + MG_BM - 1) / MG_BM, cb = (o2 - o1 + MG_BM - 1) / MG_BM;
+  int incl = ca + cb;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  const int excl = incl - ca - cb;
+  const bool hit = t >= excl && t < incl;
+  const uint64_t bal = __ballot(hit);
+  if (bal == 0) return false;
+  const int src = __ffsll((unsigned long long)bal) - 1;
+  const bool second = t >= excl + ca;
+  const int me = second ? eb : ea;
+  const int mr = (second ? o1 : o0) + (t - excl - (second ? ca : 0)) * MG_BM;
+  const int ms = second ? o2 : o1;
+  e = __shfl(me, src, 64);
+  r0 = __shfl(mr, src, 64);
+  s1 = __shfl(ms, src, 64);
+  return true;
+}
+
+template <bool SWIGLU>
+__global__ __launch_bounds__(256) void moe_gemm_tiled_k(const bf16* __restrict__ A, const int* __restrict__ perm,
+                                                        int kdiv, const int* __restrict__ offsets,
+                                                        const bf16* __restrict__ W, bf16* __restrict__ out, int E,
+                                                        int N, int K, int nblk) {
+  __shared__ __attribute__((aligned(16))) bf16 sx[2][MG_BM * MG_BK];
+  __shared__ __attribute__((aligned(16))) bf16 sw[2][MG_BN * MG_BK];
+  int e, r0, s1;
+  if (!find_tile(offsets, E, blockIdx.x / nblk, e, r0, s1)) return;
+  const int bn = blockIdx.x % nblk;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
+  const int wm = w >> 1, wn = w & 1;          // 2 × 2 waves: 32 rows × 64 weight rows each
+  const int cols = SWIGLU ? 64 : 128;         // logical output columns per workgroup
+  const bf16* We = W + (size_t)e * (SWIGLU ? 2 : 1) * N * K;
+
+  // DMA sources.  A wave instruction fills 8 rows × 8 slots; row r, slot s ← chunk s ^ (r & 7) of that row.
+  const int sl = lane & 7;
+  const bf16* xsrc[2];
+  int xchk[2], wchk[4];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = (q * 4 + w) * 8 + (lane >> 3);
+    const int p = min(r0 + r, s1 - 1);
+    xsrc[q] = A + (size_t)(perm ? perm[p] / kdiv : p) * K;
+    xchk[q] = 8 * (sl ^ (r & 7));
+  }
+  const bf16* wsrc[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = (q * 4 + w) * 8 + (lane >> 3);          // tile row 0..127
+    int n;                                                // row of this expert's weight matrix
+    if (SWIGLU) n = (r >= 64 ? N : 0) + min(bn * 64 + (r & 63), N - 1);
+    else n = min(bn * 128 + r, N - 1);
+    wsrc[q] = We + (size_t)n * K;
+    wchk[q] = 8 * (sl ^ (r & 7));
+  }
+  // K % 64 == 32 (I = 96): the last stage is half wide; its upper chunks re-read the lower ones (in bounds, unused)
+  auto koff = [&](int k0, int chk) { return k0 + chk < K ? k0 + chk : k0 + chk - 32; };
+  auto issue = [&](int buf, int k0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) dma16(xsrc[q] + koff(k0, xchk[q]), &sx[buf][(q * 4 + w) * 8 * MG_BK]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dma16(wsrc[q] + koff(k0, wchk[q]), &sw[buf][(q * 4 + w) * 8 * MG_BK]);
+  };
+
+  // fragment j of this wave → tile row of W.  SWIGLU: j = 2c + {0 gate, 1 up} for column group c = 0, 1
+  int frow[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) frow[j] = SWIGLU ? (j & 1) * 64 + wn * 32 + (j >> 1) * 16 : wn * 64 + 16 * j;
+
+  f32x4 acc[4][2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) acc[j][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = (K + MG_BK - 1) / MG_BK;
+  issue(0, 0);
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this lane's part of stage kt has landed
+    __syncthreads();                                        // stage kt visible; every wave is done reading stage kt-1
+    if (kt + 1 < nk) issue(buf ^ 1, (kt + 1) * MG_BK);      // flies under this stage's MFMAs
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      if (kt * MG_BK + 32 * ks >= K) break;
+      const int c = ks * 4 + g;
+      bf16x8 b[2], a[4];
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        const int r = wm * 32 + mi * 16 + li;
+        b[mi] = *reinterpret_cast<const bf16x8*>(&sx[buf][r * MG_BK + 8 * (c ^ (r & 7))]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = frow[j] + li;
+        a[j] = *reinterpret_cast<const bf16x8*>(&sw[buf][r * MG_BK + 8 * (c ^ (r & 7))]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+          acc[j][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], b[mi], acc[j][mi], 0, 0, 0);
+    }
+  }
+
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi) {
+    const int p = r0 + wm * 32 + mi * 16 + li;
+    if (p >= s1) continue;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      // SWIGLU: fragments (2c, 2c+1) = gate / up of columns wn·32 + 16c; DOWN: columns wn·64 + 32c (+16)
+      const int col0 = bn * cols + (SWIGLU ? wn * 32 + 16 * c : wn * 64 + 32 * c) + 4 * g;
+      if (col0 >= N) continue;
+      store_pair<SWIGLU>(out, N, p, col0, col0 + 16, acc[2 * c][mi], acc[2 * c + 1][mi]);
+    }
+  }
+}
+
+}  // namespace
+
+// Row class from (P, E) alone: 1 = skinny while an average segment fits one 64-row pass twice over, else 2 = tiled.
+int moe_gemm_class(int P, int E) { return (long long)P <= 32LL * E ? 1 : 2; }
+
+// stage 0: A = x [T, K=H], perm [P], W = w13 [E, 2N, K], out = hs [P, N=I]
+// stage 1: A = hs [P, K=I], perm = nullptr, W = w2 [E, N=H, K], out = ys [P, N]
+void launch_moe_gemm(int stage, int cls, const void* A, const int* perm, int kdiv, const int* offsets, const void* W,
+                     void* out, int P, int E, int N, int K, hipStream_t st) {
+  const int nblk = stage == 0 ? (N + 63) / 64 : (N + 127) / 128;
+  if (cls == 1) {
+    const int grid = E * nblk;
+    if (stage == 0)
+      moe_gemm_skinny_k<true><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out, N,
+                                                    K, nblk);
+    else
+      moe_gemm_skinny_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out,
+                                                     N, K, nblk);
+  } else {
+    const int tiles = P < P / MG_BM + E ? P : P / MG_BM + E;     // >= Σ_e ceil(c_e / BM) for every routing
+    const int grid = tiles * nblk;
+    if (stage == 0)
+      moe_gemm_tiled_k<true><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out, E,
+                                                   N, K, nblk);
+    else
+      moe_gemm_tiled_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out, E,
+                                                    N, K, nblk);
+  }
+  LIPA_CHECK_LAUNCH();
+}

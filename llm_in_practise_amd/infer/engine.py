@@ -24,6 +24,8 @@ Streaming requests receive text deltas per token; ``/metrics`` data (Prometheus 
 from __future__ import annotations
 
 import dataclasses
+import json
+import os
 import queue
 import threading
 import time
@@ -399,6 +401,28 @@ def check_kv_fp8_config(head_dim: int, tp: int = 1, pp: int = 1, kv_remote: bool
         raise ValueError(f"--kv-cache-dtype fp8 needs a head dim of 64 or 128, the model has {head_dim}")
 
 
+_MOE_LORA_OK = {"q_proj", "k_proj", "v_proj", "o_proj"}
+
+
+def check_moe_serving(tp: int = 1, pp: int = 1, quant: str | None = None, adapters=()):
+    """Start-up rejections for a Qwen3-MoE model (``num_experts`` > 0); every message names the flag.  ``adapters``:
+    LoRA adapter directories; one that targets anything but the attention projections is refused."""
+    if tp > 1:
+        raise ValueError("Qwen3-MoE does not support --tensor-parallel-size (-tp) > 1: the experts are not sharded")
+    if pp > 1:
+        raise ValueError("Qwen3-MoE does not support --pipeline-parallel-size (-pp) > 1")
+    if quant:
+        raise ValueError(f"Qwen3-MoE does not support --quantization / --quant {quant}: the expert GEMMs are bf16")
+    for path in adapters:
+        with open(os.path.join(path, "adapter_config.json")) as f:
+            tm = json.load(f).get("target_modules") or []
+        bad = sorted({str(t).split(".")[-1] for t in ([tm] if isinstance(tm, str) else tm)} - _MOE_LORA_OK)
+        if bad:
+            raise ValueError(f"Qwen3-MoE: --adapter / --lora-modules {path} targets {bad}; adapters may target the "
+                             f"attention projections only ({', '.join(sorted(_MOE_LORA_OK))}), not expert or router "
+                             "weights")
+
+
 class ServingEngine:
     def __init__(self, model, tokenizer, model_name: str = "lipa-model", max_batch: int = 16,
                  system_prompt: str | None = None, chat_template: str = "auto", space_before_end: bool = False,
@@ -462,6 +486,10 @@ class ServingEngine:
         self.h_latency = _Histogram([0.05, 0.1, 0.25, 0.5, 1, 2, 5, 10, 30, 60])
         self.h_ttft = _Histogram([0.01, 0.025, 0.05, 0.1, 0.2, 0.5, 1, 2, 5])
         self.queue_time_ewma: float | None = None
+        if getattr(cfg, "num_experts", 0) > 0:
+            check_moe_serving(tp=1 if tp_group is None else 2,
+                              pp=2 if getattr(self.lm.model, "pp", None) is not None else 1,
+                              adapters=list((lora_modules or {}).values()))
         self.kv_fp8 = normalize_kv_dtype(kv_cache_dtype) == "fp8"
         if self.kv_fp8:
             check_kv_fp8_config(cfg.head_dim, tp=1 if tp_group is None else 2,

@@ -28,6 +28,7 @@ from ..ops import reference as ref
 from ..ops._native import use_native
 from ..ops.activation import swiglu_fused
 from ..ops.mlp import fusable as mlp_fusable, swiglu_mlp
+from ..ops.moe import moe_experts, moe_route
 from ..ops.attention import check_cu_seqlens, flash_attention, flash_attention_prefix, flash_attention_varlen
 from ..ops.decode import decode_attention_append
 from ..ops.kv_fp8 import decode_attention_append_fp8, prefill_attention_fp8
@@ -70,11 +71,27 @@ class Qwen3Config:
     use_cache: bool = True
     attention_bias: bool = False      # Qwen2 (DeepSeek-R1-Distill-Qwen) has q/k/v biases
     qk_norm: bool = True              # Qwen3 per-head q/k RMSNorm; Qwen2 has none
+    # Qwen3-MoE (model_type "qwen3_moe"); num_experts = 0 is the dense model
+    num_experts: int = 0
+    num_experts_per_tok: int = 8
+    moe_intermediate_size: int = 768
+    norm_topk_prob: bool = False
+    decoder_sparse_step: int = 1
+    mlp_only_layers: list = dataclasses.field(default_factory=list)
+
+    def is_moe_layer(self, layer_idx: int) -> bool:
+        """HF's rule for which decoder layers carry the routed block."""
+        return (layer_idx not in self.mlp_only_layers and self.num_experts > 0
+                and (layer_idx + 1) % self.decoder_sparse_step == 0)
 
     @classmethod
     def from_dict(cls, d: dict) -> "Qwen3Config":
         fields = {f.name for f in dataclasses.fields(cls)}
         kw = {k: v for k, v in d.items() if k in fields}
+        if "num_experts" not in d and "num_local_experts" in d:    # transformers >= 5 writes the mapped name
+            kw["num_experts"] = d["num_local_experts"]
+        if kw.get("mlp_only_layers") is None:
+            kw.pop("mlp_only_layers", None)
         if d.get("model_type") == "qwen2":         # DeepSeek-R1-Distill-Qwen-*: biased qkv, no qk-norm
             kw.setdefault("attention_bias", True)
             kw["qk_norm"] = False
@@ -94,6 +111,11 @@ class Qwen3Config:
 
     def to_dict(self) -> dict:
         d = dataclasses.asdict(self)
+        if self.num_experts > 0:
+            d["architectures"] = ["Qwen3MoeForCausalLM"]
+            return d
+        for k in _MOE_FIELDS:       # a dense config reads as it always did
+            d.pop(k)
         d["architectures"] = ["Qwen2ForCausalLM" if self.model_type == "qwen2" else "Qwen3ForCausalLM"]
         return d
 
@@ -102,9 +124,14 @@ class Qwen3Config:
         d, hq, hkv = self.head_dim, self.num_attention_heads, self.num_key_value_heads
         attn = h * hq * d * 2 + h * hkv * d * 2 + (2 * d if self.qk_norm else 0)
         attn += (hq + 2 * hkv) * d if self.attention_bias else 0
-        mlp = 3 * h * f
+        moe = sum(self.is_moe_layer(i) for i in range(L))
+        mlp = (L - moe) * 3 * h * f + moe * self.num_experts * (3 * h * self.moe_intermediate_size + h)
         emb = self.vocab_size * h * (1 if self.tie_word_embeddings else 2)
-        return L * (attn + mlp + 2 * h) + emb + h
+        return L * (attn + 2 * h) + mlp + emb + h
+
+
+_MOE_FIELDS = ("num_experts", "num_experts_per_tok", "moe_intermediate_size", "norm_topk_prob", "decoder_sparse_step",
+               "mlp_only_layers")
 
 
 # [ext] public HF configs
@@ -135,6 +162,13 @@ PRESETS: dict[str, dict] = {
     "qwen3-tiny-d64": dict(vocab_size=512, hidden_size=128, intermediate_size=256, num_hidden_layers=2,
                            num_attention_heads=4, num_key_value_heads=2, head_dim=64,
                            max_position_embeddings=512),
+    # qwen3-tiny-d64 with 8 routed experts, top-2 (the smallest shapes the grouped expert GEMMs serve)
+    "qwen3-moe-tiny": dict(vocab_size=512, hidden_size=128, intermediate_size=256, num_hidden_layers=2,
+                           num_attention_heads=4, num_key_value_heads=2, head_dim=64, max_position_embeddings=512,
+                           model_type="qwen3_moe", num_experts=8, num_experts_per_tok=2, moe_intermediate_size=64),
+    "qwen3-30b-a3b": dict(hidden_size=2048, intermediate_size=6144, num_hidden_layers=48, num_attention_heads=32,
+                          num_key_value_heads=4, head_dim=128, max_position_embeddings=40960, model_type="qwen3_moe",
+                          num_experts=128, num_experts_per_tok=8, moe_intermediate_size=768, norm_topk_prob=True),
     "qwen3-small": dict(vocab_size=4096, hidden_size=1024, intermediate_size=3072, num_hidden_layers=4,
                         num_attention_heads=8, num_key_value_heads=4, head_dim=128,
                         max_position_embeddings=4096),
@@ -301,11 +335,42 @@ class Qwen3MLP(nn.Module):
         return tp_all_reduce(y, self.tp_group)
 
 
+class Qwen3MoeExperts(nn.Module):
+    """Stacked expert weights under HF's names: ``gate_up_proj`` [E, 2I, H] (gate rows, then up rows) and
+    ``down_proj`` [E, H, I]."""
+
+    def __init__(self, cfg: Qwen3Config):
+        super().__init__()
+        E, h, f = cfg.num_experts, cfg.hidden_size, cfg.moe_intermediate_size
+        self.gate_up_proj = nn.Parameter(torch.empty(E, 2 * f, h))
+        self.down_proj = nn.Parameter(torch.empty(E, h, f))
+
+
+class Qwen3MoeBlock(nn.Module):
+    """Qwen3-MoE routed block: a bias-free router over ``num_experts`` SwiGLU experts, top-k (``ops/moe.py``:
+    routing kernel, dispatch, two grouped GEMM launches, combine; nothing is read back to the host)."""
+
+    def __init__(self, cfg: Qwen3Config):
+        super().__init__()
+        self.top_k = cfg.num_experts_per_tok
+        # softmax over all experts, top-k, renormalise = softmax over the k winning logits
+        self.routing = "topk_softmax" if cfg.norm_topk_prob else "softmax_topk"
+        self.gate = nn.Linear(cfg.hidden_size, cfg.num_experts, bias=False)
+        self.experts = Qwen3MoeExperts(cfg)
+
+    def fuse(self):
+        pass
+
+    def forward(self, x, residual=None):
+        w, idx = moe_route(self.gate(x), self.top_k, self.routing)
+        return moe_experts(x, self.experts.gate_up_proj, self.experts.down_proj, idx, w, residual)
+
+
 class Qwen3DecoderLayer(nn.Module):
     def __init__(self, cfg: Qwen3Config, layer_idx: int):
         super().__init__()
         self.self_attn = Qwen3Attention(cfg, layer_idx)
-        self.mlp = Qwen3MLP(cfg)
+        self.mlp = Qwen3MoeBlock(cfg) if cfg.is_moe_layer(layer_idx) else Qwen3MLP(cfg)
         self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
@@ -424,7 +489,7 @@ class Qwen3ForCausalLM(nn.Module):
         m.to(dtype)
         with torch.no_grad():
             for n, p in m.named_parameters():
-                if p.dim() == 2:
+                if p.dim() >= 2:            # linears, embeddings and the stacked expert weights
                     p.normal_(0.0, init_std)
         return m
 
@@ -456,7 +521,8 @@ class Qwen3ForCausalLM(nn.Module):
     def invalidate_fusion(self):
         for layer in self.model.layers:
             layer.self_attn._qkv = None
-            layer.mlp._gu = None
+            if isinstance(layer.mlp, Qwen3MLP):
+                layer.mlp._gu = None
 
     # -------------------------------------------------------------- forward
     def forward(self, input_ids, attention_mask=None, labels=None, position_ids=None,
@@ -506,7 +572,20 @@ class Qwen3ForCausalLM(nn.Module):
 
     # -------------------------------------------------------------- checkpoint IO
     def load_hf_state_dict(self, sd: dict[str, torch.Tensor], strict: bool = False):
+        """Expert weights are taken stacked (``mlp.experts.gate_up_proj`` / ``down_proj``, transformers >= 5) or
+        per expert (``mlp.experts.J.{gate,up,down}_proj.weight``, the published checkpoints)."""
         own = self.state_dict()
+        if self.config.num_experts > 0 and any(".mlp.experts.0." in k for k in sd):
+            sd = dict(sd)
+            E = self.config.num_experts
+            for i, layer in enumerate(self.model.layers):
+                pre = f"model.layers.{i}.mlp.experts."
+                if not isinstance(layer.mlp, Qwen3MoeBlock) or f"{pre}0.gate_proj.weight" not in sd:
+                    continue
+                take = lambda name: [sd.pop(f"{pre}{j}.{name}.weight") for j in range(E)]     # noqa: E731
+                gate, up = take("gate_proj"), take("up_proj")
+                sd[pre + "gate_up_proj"] = torch.stack([torch.cat(gu, 0) for gu in zip(gate, up)])
+                sd[pre + "down_proj"] = torch.stack(take("down_proj"))
         missing = [k for k in own if k not in sd and "inv_freq" not in k]
         with torch.no_grad():
             for k, v in sd.items():
@@ -553,6 +632,13 @@ class Qwen3ForCausalLM(nn.Module):
         os.makedirs(path, exist_ok=True)
         sd = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()
               if "inv_freq" not in k}
+        f = self.config.moe_intermediate_size
+        for k in [k for k in sd if k.endswith(".mlp.experts.gate_up_proj")]:     # written per expert, as published
+            pre, gu, dn = k[:-len("gate_up_proj")], sd.pop(k), sd.pop(k[:-len("gate_up_proj")] + "down_proj")
+            for j in range(gu.shape[0]):
+                sd[f"{pre}{j}.gate_proj.weight"] = gu[j, :f].contiguous()
+                sd[f"{pre}{j}.up_proj.weight"] = gu[j, f:].contiguous()
+                sd[f"{pre}{j}.down_proj.weight"] = dn[j].contiguous()
         if self.config.tie_word_embeddings:
             sd.pop("lm_head.weight", None)
         shards, cur, size = [], {}, 0

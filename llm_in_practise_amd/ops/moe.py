@@ -11,6 +11,11 @@ offsets).  CPU tensors run the equivalent torch code below; both are autograd-co
     xs = moe_gather(x, d)                          # [T·k, H] rows sorted by expert
     ys = expert_i(xs[off[i]:off[i+1]]) …           # per-expert GEMMs on contiguous slices
     out = moe_combine(ys, d, w, base)              # base + Σ_j w[t,j]·ys[pos_of[t,j]]
+
+SwiGLU experts with stacked weights (Qwen3-MoE) run the whole expert MLP in two grouped launches
+(``moe_gemm.hip``) with nothing read back to the host, so a decode step stays graph-capturable:
+
+    out = moe_experts(x, w13, w2, idx, w, base)    # dispatch → gemm_swiglu → gemm_down → combine
 """
 from __future__ import annotations
 
@@ -47,7 +52,13 @@ def moe_route(logits: torch.Tensor, k: int, mode: str = "topk_softmax"):
     ``topk_softmax``: top-k of the raw logits, softmax over the k (DeepSeekLike).
     ``softmax_topk``: softmax over all experts, top-k probabilities, unnormalised (notebook)."""
     m = _MODES[mode]
-    if use_native(logits) and logits.shape[1] <= 64 and k <= 8:
+    E = logits.shape[1]
+    # 64 < E <= 128 (two experts per lane) is forward only: logits that require grad keep the torch path
+    if use_native(logits) and k <= 8 and (E <= 64 or (E <= 128 and not (logits.requires_grad and
+                                                                       torch.is_grad_enabled()))):
+        if E > 64:
+            idx, w, _ = native().moe_route(logits.contiguous(), k, m, False)
+            return w, idx.long()
         w, idx = fn_apply(_RouteFn, logits, k, m)
         return w, idx.long()
     if m == 1:
@@ -135,3 +146,62 @@ def moe_combine(ys: torch.Tensor, d: Dispatch, w: torch.Tensor, base: torch.Tens
     g = ys.index_select(0, d.pos_of.long()).view(T, d.k, -1)
     out = (g * w.to(ys.dtype).unsqueeze(-1)).sum(1)
     return out if base is None else out + base
+
+
+# ------------------------------------------------------------------ grouped SwiGLU experts
+def moe_experts_reference(x, w13, w2, idx, w, base=None):
+    """The per-pair specification of a routed SwiGLU expert block, in torch.
+
+    x [T, H]; w13 [E, 2I, H] (rows 0..I-1 gate, I..2I-1 up); w2 [E, H, I]; idx [T, k]; w [T, k]; base [T, H].
+    For each pair (t, j), e = idx[t, j]:  g, u = x[t]·w13[e]ᵀ (fp32, unrounded);  h = round(silu(g)·u);
+    y = round(h·w2[e]ᵀ);  out[t] = round(base[t] + Σ_j w[t, j]·y(t, j)) with the sum in fp32 in j order.
+    ``round`` is to x's dtype; fp64 inputs are computed in fp64 throughout (the tests' oracle).  Pairs of one
+    expert are computed together, which changes nothing per pair.  Differentiable."""
+    T, k = idx.shape
+    I = w2.shape[2]
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    flat = idx.reshape(-1)
+    tok = torch.arange(T * k, device=x.device) // k
+    ys = torch.zeros(T * k, x.shape[1], dtype=x.dtype, device=x.device)
+    for e in torch.unique(flat).tolist():
+        rows = (flat == e).nonzero().squeeze(1)
+        gu = x[tok[rows]].to(acc) @ w13[e].to(acc).t()
+        h = (F.silu(gu[:, :I]) * gu[:, I:]).to(x.dtype)
+        ys = ys.index_copy(0, rows, (h.to(acc) @ w2[e].to(acc).t()).to(x.dtype))
+    out = torch.zeros(T, x.shape[1], dtype=acc, device=x.device) if base is None else base.to(acc)
+    ys = ys.view(T, k, -1)
+    for j in range(k):
+        out = out + w[:, j:j + 1].to(acc) * ys[:, j].to(acc)
+    return out.to(x.dtype)
+
+
+def moe_gemm_supported(x, w13, w2) -> bool:
+    """Shapes and dtypes the grouped kernels serve: bf16, E <= 128, H % 64 == 0, I % 32 == 0."""
+    E, I2, H = w13.shape
+    return (x.dtype == w13.dtype == w2.dtype == torch.bfloat16 and x.dim() == 2 and E <= 128 and H % 64 == 0
+            and I2 % 64 == 0 and tuple(w2.shape) == (E, H, I2 // 2))
+
+
+def moe_gemm_swiglu(x, d: Dispatch, w13, row_class: int = 0):
+    """hs [T·k, I] in expert-sorted order: row p = bf16(silu(g)·u) of x[perm[p] // k] through expert e's w13."""
+    return native().moe_gemm_swiglu(x.contiguous(), d.perm, d.offsets, w13.contiguous(), d.k, row_class)
+
+
+def moe_gemm_down(hs, d: Dispatch, w2, row_class: int = 0):
+    """ys [T·k, H]: row p = bf16(hs[p] · w2[e]ᵀ) for the expert e whose segment holds p."""
+    return native().moe_gemm_down(hs, d.offsets, w2.contiguous(), row_class)
+
+
+def moe_experts(x, w13, w2, idx, w, base=None, row_class: int = 0):
+    """Routed SwiGLU experts: ``base + Σ_j w[t, j] · expert_{idx[t, j]}(x[t])`` (see ``moe_experts_reference``).
+
+    On HIP tensors: dispatch, two grouped GEMM launches and the combine, with no host read of the routing.
+    ``row_class`` (1 skinny / 2 tiled) overrides the class the kernels pick from (T·k, E); tests only.
+    CPU tensors, ``LIPA_REFERENCE=1``, unsupported shapes and inputs that require grad run the reference."""
+    grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w13, w2, w, base))
+    if not use_native(x) or grad or not moe_gemm_supported(x, w13, w2) or idx.numel() == 0:
+        return moe_experts_reference(x, w13, w2, idx, w, base)
+    d = moe_dispatch(idx, w13.shape[0])
+    hs = moe_gemm_swiglu(x, d, w13, row_class)
+    ys = moe_gemm_down(hs, d, w2, row_class)
+    return moe_combine(ys, d, w, base)

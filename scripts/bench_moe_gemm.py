@@ -1,0 +1,103 @@
+"""The routed expert MLP of a Qwen3-30B-A3B layer (E 128, top-8, H 2048, I 768): ``moe_experts`` (dispatch, two grouped
+GEMM launches of moe_gemm.hip, combine) against the per-expert loop it replaces (dispatch, gather, one host read of
+the segment offsets, two torch GEMMs and a SwiGLU per live expert, combine), one process, interleaved round by round.
+
+    python scripts/bench_moe_gemm.py [--out profiles/r13/moe_gemm.txt]
+
+Per T: device-event time of >= ITERS back-to-back calls (>= 50 ms) per round, ROUNDS rounds alternating the two;
+reported: the median of the round medians with min .. max.  Routing is uniform random; every call takes the next of
+NROUTE routings, so that successive calls stream different experts (the 1.2 GB of expert weights do not fit the 256 MB
+of L2 + MALL; one routing's 8 live experts at T = 1 would).  For the skinny class the live experts' weight bytes
+(distinct experts × 3·H·I·2, mean over the routings) over the grouped time are given as GB/s: it is the whole op's
+time, launches of dispatch and combine included, not a kernel's.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from llm_in_practise_amd.ops import moe  # noqa: E402
+from llm_in_practise_amd.ops._native import native  # noqa: E402
+
+E, K, H, I = 128, 8, 2048, 768
+ROUNDS, ITERS, NROUTE = 7, 10, 16
+
+
+def expert_loop(x, w13, w2, idx, w):
+    d = moe.moe_dispatch(idx, E)
+    xs = moe.moe_gather(x, d)
+    ys, s = [], 0
+    for e, c in enumerate(d.counts()):          # the host read
+        if c:
+            gu = F.linear(xs[s:s + c], w13[e])
+            ys.append(F.linear(F.silu(gu[:, :I]) * gu[:, I:], w2[e]))
+        s += c
+    return moe.moe_combine(torch.cat(ys, 0), d, w, None)
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(iters):
+        fn(i)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters * 1e3      # µs per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--tokens", type=int, nargs="+", default=[1, 8, 64, 256, 2048])
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_moe_gemm: needs the GPU (no CPU fall-back for a timing)")
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    w13 = (torch.randn(E, 2 * I, H, device=dev, generator=g) * H ** -0.5).bfloat16()
+    w2 = (torch.randn(E, H, I, device=dev, generator=g) * I ** -0.5).bfloat16()
+    lines = [f"routed expert MLP, E {E} top-{K} H {H} I {I}, bf16; {ROUNDS} rounds x >= {ITERS} calls (>= 50 ms), "
+             f"loop / grouped interleaved, {NROUTE} uniform routings in turn",
+             f"{'T':>5} {'class':>6} | {'per-expert loop us (min..max)':>34} | {'grouped us (min..max)':>30} | "
+             f"{'grouped/loop':>12} | live experts, weight GB/s (grouped)"]
+    for T in a.tokens:
+        x = torch.randn(T, H, device=dev, generator=g).bfloat16()
+        routes = []
+        for _ in range(NROUTE):
+            idx = torch.rand(T, E, device=dev, generator=g).topk(K, -1).indices
+            routes.append((idx, torch.rand(T, K, device=dev, generator=g)))
+        live = statistics.mean(len(torch.unique(idx)) for idx, _ in routes)
+        fns = {"loop": lambda i: expert_loop(x, w13, w2, *routes[i % NROUTE]),
+               "grouped": lambda i: moe.moe_experts(x, w13, w2, *routes[i % NROUTE])}
+        diff = (fns["loop"](0).float() - fns["grouped"](0).float()).abs().max().item()
+        for fn in fns.values():
+            for i in range(NROUTE):
+                fn(i)
+        torch.cuda.synchronize()
+        iters = max(ITERS, min(1000, int(5e4 / timed(fns["grouped"], ITERS))))
+        t = {"loop": [], "grouped": []}
+        for _ in range(ROUNDS):
+            for name, fn in fns.items():
+                t[name].append(timed(fn, iters))
+        med = {n: statistics.median(v) for n, v in t.items()}
+        cell = {n: f"{med[n]:9.1f} ({min(t[n]):.1f}..{max(t[n]):.1f})" for n in t}
+        cls = "skinny" if native().moe_gemm_class(T * K, E) == 1 else "tiled"
+        gbs = f"{live:6.1f}, {live * 3 * H * I * 2 / med['grouped'] / 1e3:6.0f}" if cls == "skinny" else f"{live:6.1f}"
+        lines.append(f"{T:>5} {cls:>6} | {cell['loop']:>34} | {cell['grouped']:>30} | {med['grouped'] / med['loop']:>12.3f} | "
+                     f"{gbs}   (max |loop - grouped| {diff:.2e})")
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -285,9 +285,37 @@ def _is_moe(path: str) -> bool:
     return d.get("model_type") == "qwen3_moe" or (d.get("num_experts") or d.get("num_local_experts") or 0) > 0
 
 
-def _load_for_inference(path, adapter=None, device=None, quant=None, fuse=True, tp_group=None, pp_group=None):
+def _moe_expert_dtype_compat(a):
+    """``--moe-expert-dtype``: every spelling → ``a.moe_expert_dtype`` ∈ {"bf16", "fp8"}; what FP8 experts do not
+    serve is refused here, before a model is loaded (the H / I the kernels serve are checked once it is)."""
+    from ..infer.engine import check_moe_fp8_config
+    from ..models.common import normalize_moe_expert_dtype
+    try:
+        a.moe_expert_dtype = normalize_moe_expert_dtype(getattr(a, "moe_expert_dtype", None))
+        path = getattr(a, "model", None) or getattr(a, "base", None)
+        if a.moe_expert_dtype == "fp8":
+            check_moe_fp8_config(1 if path and _is_moe(path) else 0, tp=int(getattr(a, "tp", None) or 1),
+                                 pp=int(getattr(a, "pp", None) or 1))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return a
+
+
+def _load_for_inference(path, adapter=None, device=None, quant=None, fuse=True, tp_group=None, pp_group=None,
+                        moe_expert_dtype=None):
     from ..models.qwen3 import BitsAndBytesConfig, Qwen3ForCausalLM, qwen3_config
     dev = device or _device()
+    moe_fp8 = False
+    if moe_expert_dtype is not None:
+        from ..infer.engine import check_moe_fp8_config
+        from ..models.common import normalize_moe_expert_dtype
+        try:
+            moe_fp8 = normalize_moe_expert_dtype(moe_expert_dtype) == "fp8"
+            if moe_fp8:
+                check_moe_fp8_config(1 if _is_moe(path) else 0, tp=1 if tp_group is None else 2,
+                                     pp=1 if pp_group is None else 2)
+        except ValueError as e:
+            raise SystemExit(str(e))
     if _is_moe(path):       # Qwen3-MoE: one GPU, bf16 experts, attention-only adapters; refused before anything loads
         from ..infer.engine import check_moe_serving
         stored = None
@@ -323,6 +351,8 @@ def _load_for_inference(path, adapter=None, device=None, quant=None, fuse=True, 
         return m.eval()
     if path.startswith("random:"):
         m = Qwen3ForCausalLM.from_config(qwen3_config(path[7:]), dtype=torch.bfloat16, device=dev)
+        if moe_fp8:                     # after initialisation, layer by layer
+            m.quantize_experts_fp8()
     else:
         with open(os.path.join(path, "config.json")) as f:
             qc = json.load(f).get("quantization_config")
@@ -331,8 +361,12 @@ def _load_for_inference(path, adapter=None, device=None, quant=None, fuse=True, 
             m = load_quantized(path, dev)
         else:
             bnb = BitsAndBytesConfig(load_in_4bit=True) if quant == "nf4" else None
-            m = Qwen3ForCausalLM.from_pretrained(path, dtype=torch.bfloat16, device=dev, quantization_config=bnb)
-    if quant == "fp8":                  # data-free W8A8 after the bf16 load (an FP8 checkpoint already holds its codes)
+            m = Qwen3ForCausalLM.from_pretrained(path, dtype=torch.bfloat16, device=dev, quantization_config=bnb,
+                                                 moe_expert_dtype="fp8" if moe_fp8 else None)
+    if moe_fp8:                         # warns when H / I are not served and the reference path will run
+        cfg = m.config
+        check_moe_fp8_config(cfg.num_experts, cfg.hidden_size, cfg.moe_intermediate_size)
+    if quant == "fp8":                # data-free W8A8 after the bf16 load (an FP8 checkpoint already holds its codes)
         from ..quant.fp8 import Fp8Linear, quantize_model_fp8
         if not any(isinstance(mod, Fp8Linear) for mod in m.modules()):
             quantize_model_fp8(m)
@@ -360,7 +394,8 @@ def _add_parallel_args(p):
 def cmd_chat(a):
     from ..infer.engine import SamplingParams, ServingEngine
     from ..train.data import load_tokenizer
-    m = _load_for_inference(a.base, a.adapter, quant=a.quant)
+    _moe_expert_dtype_compat(a)
+    m = _load_for_inference(a.base, a.adapter, quant=a.quant, moe_expert_dtype=a.moe_expert_dtype)
     tok = load_tokenizer(a.tokenizer or a.base)
     eng = ServingEngine(m, tok, system_prompt=a.system, space_before_end=True)
     history = []                                  # multi-turn (inferences.py:77-83, 04-*-multisession*.py)
@@ -389,8 +424,10 @@ def cmd_chat(a):
 def cmd_infer(a):
     from ..infer.generate import generate
     from ..train.data import load_tokenizer, render_chatml
+    _moe_expert_dtype_compat(a)
     tp, tpg, ppg = _parallel(a)      # torchrun → TP / PP; every rank decodes in lockstep
-    m = _load_for_inference(a.model, a.adapter, quant=a.quant, tp_group=tpg, pp_group=ppg)
+    m = _load_for_inference(a.model, a.adapter, quant=a.quant, tp_group=tpg, pp_group=ppg,
+                            moe_expert_dtype=a.moe_expert_dtype)
     tok = load_tokenizer(a.tokenizer or a.model)
     text = render_chatml([{"role": "user", "content": a.prompt}], add_generation_prompt=True) if a.chat else a.prompt
     ids = torch.tensor([tok.encode(text, add_special_tokens=False)], device=_device())
@@ -550,6 +587,7 @@ def _vllm_compat(a):
     if getattr(a, "quant", None) == "fp8" and max(int(getattr(a, "tp", None) or 1), int(getattr(a, "pp", None) or 1)) > 1:
         raise SystemExit(_FP8_NO_TP)
     _kv_cache_dtype_compat(a)
+    _moe_expert_dtype_compat(a)
     if vq == "bitsandbytes":
         a.quant = "nf4"
     elif vq is not None and vq != "fp8":
@@ -584,7 +622,8 @@ def _serving_engine_from_args(a, tp=None, tpg=None, ppg=None):
     from ..infer.engine import ServingEngine
     from ..train.data import load_tokenizer
     g = lambda k, d=None: getattr(a, k, d)      # noqa: E731  (namespaces built by other commands)
-    m = _load_for_inference(a.model, g("adapter"), quant=g("quant"), tp_group=tpg, pp_group=ppg)
+    m = _load_for_inference(a.model, g("adapter"), quant=g("quant"), tp_group=tpg, pp_group=ppg,
+                            moe_expert_dtype=g("moe_expert_dtype"))
     tok = load_tokenizer(g("tokenizer") or a.model)
     if g("chat_template"):                        # vLLM --chat-template: a jinja file (or the template itself)
         path = g("chat_template")
@@ -606,7 +645,8 @@ def _serving_engine_from_args(a, tp=None, tpg=None, ppg=None):
                          chunked_prefill=g("max_batched_tokens", 2048) if g("chunked_prefill") else 0,
                          lora_modules=loras, host_cache_blocks=host_blocks,
                          kv_remote_url=g("kv_remote_url"), gpu_memory_utilization=g("gpu_memory_utilization"),
-                         use_graphs=False if g("enforce_eager") else None, kv_cache_dtype=g("kv_cache_dtype"))
+                         use_graphs=False if g("enforce_eager") else None, kv_cache_dtype=g("kv_cache_dtype"),
+                         moe_expert_dtype=g("moe_expert_dtype"))
 
 
 def _serve_task(a) -> str:
@@ -1051,6 +1091,10 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--adapter")
         p.add_argument("--tokenizer")
         p.add_argument("--quant", choices=["nf4"])
+        p.add_argument("--moe-expert-dtype", "--moe_expert_dtype", dest="moe_expert_dtype", default="auto",
+                       help="Qwen3-MoE expert weights: auto | bfloat16 (as the checkpoint holds them) or fp8 | fp8_e4m3 "
+                            "(weight-only e4m3 codes, one scale per expert row, bf16 activations: half the expert bytes; "
+                            "one GPU)")
         p.add_argument("--max_new", type=int, default=256)
         p.add_argument("--temperature", type=float, default=0.7)
         p.add_argument("--top_p", type=float, default=0.9)
@@ -1112,6 +1156,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kv-cache-dtype", "--kv_cache_dtype", dest="kv_cache_dtype", default="auto",
                    help="vLLM flag: auto | bfloat16 (the model's dtype) or fp8 | fp8_e4m3 (e4m3 codes and one scale "
                         "per token and kv head: 0.5625 of the bf16 cache bytes; one GPU, head dim 64 / 128)")
+    p.add_argument("--moe-expert-dtype", "--moe_expert_dtype", dest="moe_expert_dtype", default="auto",
+                   help="Qwen3-MoE expert weights: auto | bfloat16 (as the checkpoint holds them) or fp8 | fp8_e4m3 "
+                        "(weight-only e4m3 codes, one scale per expert row, bf16 activations: half the expert bytes; "
+                        "one GPU)")
     p.add_argument("--gpu-memory-utilization", dest="gpu_memory_utilization", type=float, default=None,
                    help="vLLM flag: fraction of device memory for weights + KV; sizes the KV slot pool")
     p.add_argument("--host", default="0.0.0.0")

@@ -103,6 +103,8 @@ void launch_moe_wgrad(int, const void*, const void*, const int*, float*, int, in
 int moe_gemm_class(int, int);
 void launch_moe_gemm(int, int, const void*, const int*, int, const int*, const void*, void*, int, int, int, int,
                      hipStream_t);
+void launch_moe_gemm_fp8(int, int, const void*, const int*, int, const int*, const void*, const float*, void*, int, int,
+                         int, int, hipStream_t);
 int lora_acc_chunks(int M, int K);
 void launch_lora_proj2(const void*, int, const void*, const void*, int, int, int, float*, int, void*, int, int, uint64_t, float, float,
                        uint64_t, float, float, size_t, uint8_t*, float*, hipStream_t);
@@ -2242,6 +2244,57 @@ Tensor moe_gemm_down(Tensor hs, Tensor offsets, Tensor w2, int64_t row_class) {
   return ys;
 }
 
+// ---- the same two stages over e4m3 expert weights: codes [E, NW, K] + fp32 scale [E, NW] (W8A16, moe_gemm.hip)
+namespace {
+void moe_gemm_fp8_check(const char* who, const Tensor& a, const Tensor& offsets, const Tensor& c, const Tensor& s,
+                        int64_t H, int64_t I) {
+  TORCH_CHECK(a.is_cuda() && c.is_cuda() && s.is_cuda() && offsets.is_cuda(), who, ": device tensors");
+  TORCH_CHECK(a.scalar_type() == at::kBFloat16, who, ": bf16 activations");
+  TORCH_CHECK(c.scalar_type() == at::kFloat8_e4m3fn || c.scalar_type() == at::kByte, who, ": codes must be e4m3");
+  TORCH_CHECK(c.is_contiguous() && s.is_contiguous(), who, ": codes and scales must be contiguous");
+  TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.dim() == 1 && offsets.is_contiguous(), who,
+              ": offsets int32 [E+1]");
+  TORCH_CHECK(c.dim() == 3 && c.size(0) == offsets.numel() - 1 && c.size(0) >= 1 && c.size(0) <= 128, who,
+              ": 1 <= E <= 128 experts, offsets [E+1]");
+  TORCH_CHECK(s.scalar_type() == at::kFloat && s.dim() == 2 && s.size(0) == c.size(0) && s.size(1) == c.size(1), who,
+              ": scales fp32 [E, rows], one per code row");
+  TORCH_CHECK(H % 64 == 0 && I % 64 == 0 && H > 0 && I > 0, who, ": H % 64 == 0 and I % 64 == 0");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(s.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              who, ": 16-byte aligned operands");
+}
+}  // namespace
+
+Tensor moe_gemm_swiglu_fp8(Tensor x, Tensor perm, Tensor offsets, Tensor c13, Tensor s13, int64_t k,
+                           int64_t row_class) {
+  CHECK_CONTIG(x); CHECK_CONTIG(perm);
+  TORCH_CHECK(x.dim() == 2 && c13.dim() == 3 && c13.size(2) == x.size(1) && c13.size(1) % 2 == 0,
+              "moe_gemm_swiglu_fp8: x [T, H], c13 [E, 2I, H]");
+  const int64_t H = x.size(1), I = c13.size(1) / 2;
+  moe_gemm_fp8_check("moe_gemm_swiglu_fp8", x, offsets, c13, s13, H, I);
+  TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == at::kInt && k >= 1 && perm.numel() == x.size(0) * k &&
+              perm.numel() < (1 << 24), "moe_gemm_swiglu_fp8: perm int32 [T*k]");
+  const int P = perm.numel(), E = c13.size(0);
+  Tensor hs = torch::empty({P, I}, x.options());
+  if (P) launch_moe_gemm_fp8(0, moe_gemm_pick(row_class, P, E), x.data_ptr(), perm.data_ptr<int>(), (int)k,
+                             offsets.data_ptr<int>(), c13.data_ptr(), s13.data_ptr<float>(), hs.data_ptr(), P, E,
+                             (int)I, (int)H, stream());
+  return hs;
+}
+
+Tensor moe_gemm_down_fp8(Tensor hs, Tensor offsets, Tensor c2, Tensor s2, int64_t row_class) {
+  CHECK_CONTIG(hs);
+  TORCH_CHECK(hs.dim() == 2 && c2.dim() == 3 && c2.size(2) == hs.size(1), "moe_gemm_down_fp8: hs [P, I], c2 [E, H, I]");
+  const int64_t H = c2.size(1), I = hs.size(1);
+  moe_gemm_fp8_check("moe_gemm_down_fp8", hs, offsets, c2, s2, H, I);
+  TORCH_CHECK(hs.size(0) < (1 << 24), "moe_gemm_down_fp8: < 2^24 rows");
+  const int P = hs.size(0), E = c2.size(0);
+  Tensor ys = torch::empty({P, H}, hs.options());
+  if (P) launch_moe_gemm_fp8(1, moe_gemm_pick(row_class, P, E), hs.data_ptr(), nullptr, 1, offsets.data_ptr<int>(),
+                             c2.data_ptr(), s2.data_ptr<float>(), ys.data_ptr(), P, E, (int)H, (int)I, stream());
+  return ys;
+}
+
 int64_t moe_gemm_class_py(int64_t P, int64_t E) { return moe_gemm_class((int)P, (int)E); }
 
 // ------------------------------------------------------------------ custom all-reduce (allreduce.hip)
@@ -2303,6 +2356,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gemm_swiglu", &moe_gemm_swiglu, py::arg("x"), py::arg("perm"), py::arg("offsets"), py::arg("w13"),
         py::arg("k"), py::arg("row_class") = 0);
   m.def("moe_gemm_down", &moe_gemm_down, py::arg("hs"), py::arg("offsets"), py::arg("w2"), py::arg("row_class") = 0);
+  m.def("moe_gemm_swiglu_fp8", &moe_gemm_swiglu_fp8, py::arg("x"), py::arg("perm"), py::arg("offsets"),
+        py::arg("c13"), py::arg("s13"), py::arg("k"), py::arg("row_class") = 0);
+  m.def("moe_gemm_down_fp8", &moe_gemm_down_fp8, py::arg("hs"), py::arg("offsets"), py::arg("c2"), py::arg("s2"),
+        py::arg("row_class") = 0);
   m.def("moe_gemm_class", &moe_gemm_class_py);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("layernorm_fwd", &layernorm_fwd);

@@ -30,6 +30,22 @@
 //    a 1-KiB run, so the XOR swizzle that keeps the 16-row fragment reads off the same banks is applied on
 //    the global side: slot s of row r holds 16-B chunk s ^ (r & 7).  Ragged last row tiles and ragged N
 //    blocks are clamped on load and masked on store, never padded in memory.
+//
+// FP8 expert weights (W8A16; moe_gemm_*_fp8_k).  W holds e4m3 codes with one fp32 scale per (expert, weight row),
+// quantised by quant/fp8.py::quantize_rows_reference; activations stay bf16.  Every finite e4m3 value is exact in
+// bf16, so the codes are converted in registers (v_cvt_pk_f32_fp8, then the upper halves) and go through the same
+// v_mfma_f32_16x16x32_bf16; the scale multiplies the fp32 accumulator in the epilogue (g and u separately, before
+// SwiGLU; their scales sit I rows apart), so a weight is never rounded a second time.  Grids, row classes, the
+// ascending K loop into one accumulator and the row-invariance of the bf16 kernels are kept; H % 64 == I % 64 == 0.
+//
+//  * skinny: a lane's 16-byte load is 16 codes = its A operand of TWO 32-deep k-steps.  Lane group g of row li
+//    reads bytes 64s + 16g .. + 15; codes 0..7 feed step 2s, codes 8..15 step 2s + 1, and x is read with the same
+//    address function (k = 64s + 16g + 8h + i), which is all a dot product needs.  Eight loads per fragment stay
+//    in flight as before, so one batch covers 512 of K instead of 256; conversion runs under the next loads.
+//  * tiled: LDS-DMA moves bytes and cannot convert, so a W stage (128 rows × 64 codes = 8 KiB, half the bf16
+//    bytes) goes global → registers one stage ahead, is converted ONCE per workgroup (two 16-byte loads, two cvt16
+//    and four ds_write_b128 per thread) and is written as the same swizzled bf16 image; fragment reads and the
+//    MFMA loop are those of the bf16 kernel.  The gathered x rows keep going by LDS-DMA.
 #include "common.h"
 
 using namespace lipa;
@@ -271,6 +287,233 @@ __global__ __launch_bounds__(256) void moe_gemm_tiled_k(const bf16* __restrict__
   }
 }
 
+// ================================================================== FP8 (e4m3) expert weights, W8A16
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int MG8_LS = 8;     // skinny: 16-byte code loads per fragment and batch (16 k-steps, 512 of K)
+
+// 16 e4m3 codes → 2 × 8 bf16, exact (every finite e4m3 value has 3 mantissa bits)
+__device__ __forceinline__ void cvt16(const u32x4& c, bf16x8& a, bf16x8& b) {
+  float f[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], true);
+    f[4 * i] = lo[0]; f[4 * i + 1] = lo[1]; f[4 * i + 2] = hi[0]; f[4 * i + 3] = hi[1];
+  }
+  a = bf16x8{(bf16)f[0], (bf16)f[1], (bf16)f[2], (bf16)f[3], (bf16)f[4], (bf16)f[5], (bf16)f[6], (bf16)f[7]};
+  b = bf16x8{(bf16)f[8], (bf16)f[9], (bf16)f[10], (bf16)f[11], (bf16)f[12], (bf16)f[13], (bf16)f[14], (bf16)f[15]};
+}
+
+// the row scales of an accumulator fragment meet the fp32 sum: acc[i] ↔ weight row n0 + i
+__device__ __forceinline__ f32x4 scaled(const f32x4& a, const f32x4& s) {
+  return f32x4{a[0] * s[0], a[1] * s[1], a[2] * s[2], a[3] * s[3]};
+}
+
+// ------------------------------------------------------------------ skinny, codes
+// As skinny_rows, with wr0 / wr1 pointing at code bytes.  Lane (li, g) loads bytes 64s + 16g .. + 15 of weight row
+// li: codes 0..7 are its A operand of k-step 2s, codes 8..15 of k-step 2s + 1, and the x rows are read at the
+// same k (64s + 16g + 8h + i), so both operands of an MFMA step hold the same 32 k-values in the same slots.
+template <bool SWIGLU, int MT>
+__device__ __forceinline__ void skinny8_rows(const bf16* __restrict__ A, const int* __restrict__ perm, int kdiv,
+                                             const uint8_t* wr0, const uint8_t* wr1, const f32x4& sc0,
+                                             const f32x4& sc1, bf16* __restrict__ out, int ldo, int K, int r0, int r1,
+                                             int col0, int col1) {
+  const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+  const bf16* xr[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int p = min(r0 + 16 * mt + li, r1 - 1);
+    xr[mt] = A + (size_t)(perm ? perm[p] / kdiv : p) * K + 16 * g;
+  }
+  f32x4 acc[2][MT];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kb = 0; kb < K; kb += 64 * MG8_LS) {
+    const int ns = min(MG8_LS, (K - kb) / 64);
+    u32x4 c0[MG8_LS], c1[MG8_LS];
+#pragma unroll
+    for (int s = 0; s < MG8_LS; ++s)
+      if (s < ns) {
+        c0[s] = *reinterpret_cast<const u32x4*>(wr0 + kb + 64 * s);
+        c1[s] = *reinterpret_cast<const u32x4*>(wr1 + kb + 64 * s);
+      }
+#pragma unroll
+    for (int s = 0; s < MG8_LS; ++s)
+      if (s < ns) {
+        bf16x8 a0[2], a1[2];
+        cvt16(c0[s], a0[0], a0[1]);
+        cvt16(c1[s], a1[0], a1[1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            const bf16x8 b = *reinterpret_cast<const bf16x8*>(xr[mt] + kb + 64 * s + 8 * h);
+            acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[h], b, acc[0][mt], 0, 0, 0);
+            acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[h], b, acc[1][mt], 0, 0, 0);
+          }
+      }
+  }
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int p = r0 + 16 * mt + li;
+    if (p < r1)
+      store_pair<SWIGLU>(out, ldo, p, col0 + 4 * g, col1 + 4 * g, scaled(acc[0][mt], sc0), scaled(acc[1][mt], sc1));
+  }
+}
+
+// W [E, NW, K] e4m3 codes, scale fp32 [E, NW]; everything else as moe_gemm_skinny_k.  K % 64 == 0, N % 64 == 0.
+template <bool SWIGLU>
+__global__ __launch_bounds__(256) void moe_gemm_skinny_fp8_k(const bf16* __restrict__ A, const int* __restrict__ perm,
+                                                             int kdiv, const int* __restrict__ offsets,
+                                                             const uint8_t* __restrict__ W,
+                                                             const float* __restrict__ scale, bf16* __restrict__ out,
+                                                             int N, int K, int nblk) {
+  const int e = blockIdx.x / nblk, bn = blockIdx.x % nblk;
+  const int s0 = offsets[e], s1 = offsets[e + 1];
+  if (s1 <= s0) return;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+  const int col0 = SWIGLU ? bn * 64 + 16 * w : bn * 128 + 32 * w;
+  const int col1 = SWIGLU ? col0 : col0 + 16;
+  if (col0 >= N) return;                    // N % 64 == 0: a wave is wholly in or out
+  const int NW = (SWIGLU ? 2 : 1) * N, n0 = col0, n1 = SWIGLU ? N + col0 : col1;
+  const uint8_t* We = W + (size_t)e * NW * K;
+  const float* se = scale + (size_t)e * NW;
+  const uint8_t* wr0 = We + (size_t)(n0 + li) * K + 16 * g;
+  const uint8_t* wr1 = We + (size_t)(n1 + li) * K + 16 * g;
+  const f32x4 sc0 = *reinterpret_cast<const f32x4*>(se + n0 + 4 * g);
+  const f32x4 sc1 = *reinterpret_cast<const f32x4*>(se + n1 + 4 * g);
+  for (int r0 = s0; r0 < s1; r0 += 64) {
+    const int r1 = min(s1, r0 + 64), n = r1 - r0;
+    if (n <= 16) skinny8_rows<SWIGLU, 1>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, N, K, r0, r1, col0, col1);
+    else if (n <= 32) skinny8_rows<SWIGLU, 2>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, N, K, r0, r1, col0, col1);
+    else skinny8_rows<SWIGLU, 4>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, N, K, r0, r1, col0, col1);
+  }
+}
+
+// ------------------------------------------------------------------ tiled, codes
+// As moe_gemm_tiled_k, except for how a W stage reaches LDS: the 128 × 64 code bytes of stage kt + 1 are loaded
+// into registers (two 16-byte loads per thread: row tid/4 (+64), quarter tid%4) while stage kt's MFMAs run, are
+// converted once, and are written as the two bf16 chunks 2q, 2q + 1 of the swizzled image the DMA would have
+// written.  The gathered x rows keep going by LDS-DMA.  One barrier per stage, as before.
+template <bool SWIGLU>
+__global__ __launch_bounds__(256) void moe_gemm_tiled_fp8_k(const bf16* __restrict__ A, const int* __restrict__ perm,
+                                                            int kdiv, const int* __restrict__ offsets,
+                                                            const uint8_t* __restrict__ W,
+                                                            const float* __restrict__ scale, bf16* __restrict__ out,
+                                                            int E, int N, int K, int nblk) {
+  __shared__ __attribute__((aligned(16))) bf16 sx[2][MG_BM * MG_BK];
+  __shared__ __attribute__((aligned(16))) bf16 sw[2][MG_BN * MG_BK];
+  int e, r0, s1;
+  if (!find_tile(offsets, E, blockIdx.x / nblk, e, r0, s1)) return;
+  const int bn = blockIdx.x % nblk;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
+  const int wm = w >> 1, wn = w & 1;
+  const int cols = SWIGLU ? 64 : 128;
+  const int NW = (SWIGLU ? 2 : 1) * N;
+  const uint8_t* We = W + (size_t)e * NW * K;
+  const float* se = scale + (size_t)e * NW;
+
+  const int sl = lane & 7;
+  const bf16* xsrc[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = (q * 4 + w) * 8 + (lane >> 3);
+    const int p = min(r0 + r, s1 - 1);
+    xsrc[q] = A + (size_t)(perm ? perm[p] / kdiv : p) * K + 8 * (sl ^ (r & 7));
+  }
+  const uint8_t* wsrc[2];
+  int wdst[2][2];                                           // element offsets of this thread's two chunks in a stage
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = q * 64 + (tid >> 2), c = 2 * (tid & 3);   // tile row 0..127, first of two 8-wide chunks
+    int n;
+    if (SWIGLU) n = (r >= 64 ? N : 0) + min(bn * 64 + (r & 63), N - 1);
+    else n = min(bn * 128 + r, N - 1);
+    wsrc[q] = We + (size_t)n * K + 8 * c;
+    wdst[q][0] = r * MG_BK + 8 * (c ^ (r & 7));
+    wdst[q][1] = r * MG_BK + 8 * ((c + 1) ^ (r & 7));
+  }
+  u32x4 wreg[2];
+  auto issue_x = [&](int buf, int k0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) dma16(xsrc[q] + k0, &sx[buf][(q * 4 + w) * 8 * MG_BK]);
+  };
+  auto load_w = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) wreg[q] = *reinterpret_cast<const u32x4*>(wsrc[q] + k0);
+  };
+  auto put_w = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      bf16x8 lo, hi;
+      cvt16(wreg[q], lo, hi);
+      *reinterpret_cast<bf16x8*>(&sw[buf][wdst[q][0]]) = lo;
+      *reinterpret_cast<bf16x8*>(&sw[buf][wdst[q][1]]) = hi;
+    }
+  };
+
+  int frow[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) frow[j] = SWIGLU ? (j & 1) * 64 + wn * 32 + (j >> 1) * 16 : wn * 64 + 16 * j;
+
+  f32x4 acc[4][2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) acc[j][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = K / MG_BK;
+  issue_x(0, 0);
+  load_w(0);
+  put_w(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this lane's part of x stage kt has landed
+    __syncthreads();                                        // stage kt visible; every wave is done reading stage kt-1
+    if (kt + 1 < nk) {
+      issue_x(buf ^ 1, (kt + 1) * MG_BK);
+      load_w((kt + 1) * MG_BK);                             // both fly under this stage's MFMAs
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int c = ks * 4 + g;
+      bf16x8 b[2], a[4];
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        const int r = wm * 32 + mi * 16 + li;
+        b[mi] = *reinterpret_cast<const bf16x8*>(&sx[buf][r * MG_BK + 8 * (c ^ (r & 7))]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = frow[j] + li;
+        a[j] = *reinterpret_cast<const bf16x8*>(&sw[buf][r * MG_BK + 8 * (c ^ (r & 7))]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+          acc[j][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], b[mi], acc[j][mi], 0, 0, 0);
+    }
+    if (kt + 1 < nk) put_w(buf ^ 1);                        // nobody reads that buffer before the next barrier
+  }
+
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int col0 = bn * cols + (SWIGLU ? wn * 32 + 16 * c : wn * 64 + 32 * c) + 4 * g;
+    if (col0 >= N) continue;
+    const f32x4 sc0 = *reinterpret_cast<const f32x4*>(se + col0);
+    const f32x4 sc1 = *reinterpret_cast<const f32x4*>(se + (SWIGLU ? N + col0 : col0 + 16));
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+      const int p = r0 + wm * 32 + mi * 16 + li;
+      if (p >= s1) continue;
+      store_pair<SWIGLU>(out, N, p, col0, col0 + 16, scaled(acc[2 * c][mi], sc0), scaled(acc[2 * c + 1][mi], sc1));
+    }
+  }
+}
+
 }  // namespace
 
 // Row class from (P, E) alone: 1 = skinny while an average segment fits one 64-row pass twice over, else 2 = tiled.
@@ -298,6 +541,33 @@ void launch_moe_gemm(int stage, int cls, const void* A, const int* perm, int kdi
     else
       moe_gemm_tiled_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out, E,
                                                     N, K, nblk);
+  }
+  LIPA_CHECK_LAUNCH();
+}
+
+// The same two stages over e4m3 codes W with one fp32 scale per (expert, weight row): scale [E, 2N] / [E, N].
+// N % 64 == 0 and K % 64 == 0 (a 16-byte code load is half a 64-deep block of one row).
+void launch_moe_gemm_fp8(int stage, int cls, const void* A, const int* perm, int kdiv, const int* offsets,
+                         const void* W, const float* scale, void* out, int P, int E, int N, int K, hipStream_t st) {
+  const int nblk = stage == 0 ? (N + 63) / 64 : (N + 127) / 128;
+  const uint8_t* Wc = (const uint8_t*)W;
+  if (cls == 1) {
+    const int grid = E * nblk;
+    if (stage == 0)
+      moe_gemm_skinny_fp8_k<true><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, Wc, scale, (bf16*)out, N,
+                                                        K, nblk);
+    else
+      moe_gemm_skinny_fp8_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, Wc, scale, (bf16*)out,
+                                                         N, K, nblk);
+  } else {
+    const int tiles = P < P / MG_BM + E ? P : P / MG_BM + E;
+    const int grid = tiles * nblk;
+    if (stage == 0)
+      moe_gemm_tiled_fp8_k<true><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, Wc, scale, (bf16*)out, E,
+                                                       N, K, nblk);
+    else
+      moe_gemm_tiled_fp8_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, Wc, scale, (bf16*)out, E,
+                                                        N, K, nblk);
   }
   LIPA_CHECK_LAUNCH();
 }

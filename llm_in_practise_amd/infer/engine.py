@@ -34,7 +34,7 @@ from typing import Any
 
 import torch
 
-from ..models.common import KVCache, PackedPrefill, normalize_kv_dtype
+from ..models.common import KVCache, PackedPrefill, normalize_kv_dtype, normalize_moe_expert_dtype
 from ..ops.decode import MAX_LOGIT_BIAS, MAX_LOGPROBS, sample, sample_logprobs, sample_rows, seed_key
 from ..ops.linear import head_logits
 from ..train.data import render_chatml
@@ -412,7 +412,8 @@ def check_moe_serving(tp: int = 1, pp: int = 1, quant: str | None = None, adapte
     if pp > 1:
         raise ValueError("Qwen3-MoE does not support --pipeline-parallel-size (-pp) > 1")
     if quant:
-        raise ValueError(f"Qwen3-MoE does not support --quantization / --quant {quant}: the expert GEMMs are bf16")
+        raise ValueError(f"Qwen3-MoE does not support --quantization / --quant {quant}: the expert GEMMs are bf16 "
+                         "(weight-only FP8 experts: --moe-expert-dtype fp8)")
     for path in adapters:
         with open(os.path.join(path, "adapter_config.json")) as f:
             tm = json.load(f).get("target_modules") or []
@@ -423,6 +424,24 @@ def check_moe_serving(tp: int = 1, pp: int = 1, quant: str | None = None, adapte
                              "weights")
 
 
+def check_moe_fp8_config(num_experts: int, hidden: int = 64, inter: int = 64, tp: int = 1, pp: int = 1) -> bool:
+    """Start-up rejections of ``--moe-expert-dtype fp8``; every message names the flag.  Returns whether the FP8
+    grouped kernels serve the shapes; when they do not, a warning says that the torch reference path will run."""
+    if num_experts <= 0:
+        raise ValueError("--moe-expert-dtype fp8 needs a Qwen3-MoE model: this model has no experts")
+    if tp > 1:
+        raise ValueError("--moe-expert-dtype fp8 does not support --tensor-parallel-size > 1")
+    if pp > 1:
+        raise ValueError("--moe-expert-dtype fp8 does not support --pipeline-parallel-size > 1")
+    ok = num_experts <= 128 and hidden % 64 == 0 and inter % 64 == 0
+    if not ok:
+        import warnings
+        warnings.warn(f"--moe-expert-dtype fp8: the FP8 expert kernels serve E <= 128, H % 64 == 0 and I % 64 == 0; "
+                      f"this model has E = {num_experts}, H = {hidden}, I = {inter} and runs the torch reference "
+                      "path for its experts (slow)")
+    return ok
+
+
 class ServingEngine:
     def __init__(self, model, tokenizer, model_name: str = "lipa-model", max_batch: int = 16,
                  system_prompt: str | None = None, chat_template: str = "auto", space_before_end: bool = False,
@@ -430,9 +449,12 @@ class ServingEngine:
                  use_graphs: bool | None = None, tp_group=None, prefix_cache_blocks: int = 0,
                  prefix_block: int = 64, chunked_prefill: int = 0, lora_modules: dict[str, str] | None = None,
                  host_cache_blocks: int = 0, kv_remote_url: str | None = None,
-                 gpu_memory_utilization: float | None = None, kv_cache_dtype: str | None = None):
+                 gpu_memory_utilization: float | None = None, kv_cache_dtype: str | None = None,
+                 moe_expert_dtype: str | None = None):
         """``kv_cache_dtype``: ``--kv-cache-dtype`` (``auto`` / ``bfloat16``: the model's dtype; ``fp8`` /
         ``fp8_e4m3``: e4m3 codes with a scale per token and kv head, ``ops/kv_fp8.py``).
+        ``moe_expert_dtype``: ``--moe-expert-dtype`` (``auto`` / ``bfloat16``: the experts as loaded; ``fp8`` /
+        ``fp8_e4m3``: weight-only e4m3 experts, quantised here layer by layer unless the loader already did).
 
         ``tp_group``: the model was sharded by ``parallel.tensor_parallel`` over this group.
         The engine then runs SPMD — group rank 0 owns the request queue and broadcasts each
@@ -490,6 +512,14 @@ class ServingEngine:
             check_moe_serving(tp=1 if tp_group is None else 2,
                               pp=2 if getattr(self.lm.model, "pp", None) is not None else 1,
                               adapters=list((lora_modules or {}).values()))
+        if normalize_moe_expert_dtype(moe_expert_dtype) == "fp8":
+            check_moe_fp8_config(getattr(cfg, "num_experts", 0), cfg.hidden_size,
+                                 getattr(cfg, "moe_intermediate_size", 0), tp=1 if tp_group is None else 2,
+                                 pp=2 if getattr(self.lm.model, "pp", None) is not None else 1)
+            self.lm.quantize_experts_fp8()
+        # experts that hold e4m3 codes, whoever quantised them: K/V bits differ from the bf16 experts'
+        self.moe_fp8 = any(getattr(getattr(getattr(l, "mlp", None), "experts", None), "fp8", False)
+                           for l in getattr(getattr(self.lm, "model", None), "layers", ()))
         self.kv_fp8 = normalize_kv_dtype(kv_cache_dtype) == "fp8"
         if self.kv_fp8:
             check_kv_fp8_config(cfg.head_dim, tp=1 if tp_group is None else 2,
@@ -583,6 +613,8 @@ class ServingEngine:
                  f"{self.lm.lm_head.weight.dtype}|{block}|tp{self.tp_rank}".encode())
         if self.kv_fp8:
             h.update(b"|kv-fp8-e4m3")
+        if self.moe_fp8:
+            h.update(b"|moe-fp8-e4m3")
         params = list(self.lm.parameters())
         with torch.no_grad():
             for p in (params[0], params[-1], self.lm.lm_head.weight):

@@ -217,6 +217,22 @@ def normalize_kv_dtype(name: str | None) -> str:
     raise ValueError(f"--kv-cache-dtype {name}: expected one of {', '.join(KV_CACHE_DTYPES)}")
 
 
+MOE_EXPERT_DTYPES = ("auto", "bfloat16", "fp8", "fp8_e4m3")
+
+
+def normalize_moe_expert_dtype(name: str | None) -> str:
+    """``--moe-expert-dtype`` spellings → ``"bf16"`` (``auto`` / ``bfloat16``: the experts as the checkpoint holds
+    them) or ``"fp8"`` (``fp8`` / ``fp8_e4m3``: weight-only e4m3 experts, ``ops/moe.py``)."""
+    n = (name or "auto").lower().replace("-", "_")
+    if n in ("auto", "bfloat16", "bf16"):
+        return "bf16"
+    if n in ("fp8", "fp8_e4m3"):
+        return "fp8"
+    if n == "fp8_e5m2":
+        raise ValueError("--moe-expert-dtype fp8_e5m2 is not supported: FP8 experts are e4m3 (fp8 / fp8_e4m3)")
+    raise ValueError(f"--moe-expert-dtype {name}: expected one of {', '.join(MOE_EXPERT_DTYPES)}")
+
+
 class PackedPrefill:
     """Prefill of several prompts packed back to back — ``[1, T]`` tokens, no padding — straight
     into their KV-cache slots (the serving engine's admission path).

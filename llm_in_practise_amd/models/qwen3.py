@@ -28,7 +28,7 @@ from ..ops import reference as ref
 from ..ops._native import use_native
 from ..ops.activation import swiglu_fused
 from ..ops.mlp import fusable as mlp_fusable, swiglu_mlp
-from ..ops.moe import moe_experts, moe_route
+from ..ops.moe import moe_experts, moe_experts_fp8, moe_route
 from ..ops.attention import check_cu_seqlens, flash_attention, flash_attention_prefix, flash_attention_varlen
 from ..ops.decode import decode_attention_append
 from ..ops.kv_fp8 import decode_attention_append_fp8, prefill_attention_fp8
@@ -41,7 +41,8 @@ from ..peft.lora import LoraLayer, base_of
 from ..quant.fp8 import Fp8Linear, swiglu_quantize_rows
 from ..quant.int4 import Int4Linear
 from ..ops.embedding import Embedding
-from .common import CausalLMOutput, FusedProjection, KVCache, PackedPrefill, _leaf_linear, can_fuse, project
+from .common import (CausalLMOutput, FusedProjection, KVCache, PackedPrefill, _leaf_linear, can_fuse,
+                     normalize_moe_expert_dtype, project)
 
 # the SwiGLU MLP through ops/mlp.py's fused GEMM-epilogue kernels when it carries no adapters (the GPU tests
 # switch this off to check the fused block against separate projections + activation kernels)
@@ -339,11 +340,53 @@ class Qwen3MoeExperts(nn.Module):
     """Stacked expert weights under HF's names: ``gate_up_proj`` [E, 2I, H] (gate rows, then up rows) and
     ``down_proj`` [E, H, I]."""
 
+    _FP8_BUFFERS = ("gate_up_codes", "gate_up_scale", "down_codes", "down_scale")
+
     def __init__(self, cfg: Qwen3Config):
         super().__init__()
         E, h, f = cfg.num_experts, cfg.hidden_size, cfg.moe_intermediate_size
+        self.shape = (E, h, f)
         self.gate_up_proj = nn.Parameter(torch.empty(E, 2 * f, h))
         self.down_proj = nn.Parameter(torch.empty(E, h, f))
+
+    @property
+    def fp8(self) -> bool:
+        """Weight-only FP8 experts: e4m3 codes and fp32 row scales as buffers instead of the two bf16 Parameters."""
+        return "gate_up_codes" in self._buffers
+
+    def drop_bf16(self):
+        """Remove the bf16 Parameters and register empty FP8 buffers (before ``to_empty``: nothing is allocated
+        for the experts until :meth:`load_fp8` hands them their codes)."""
+        for name in ("gate_up_proj", "down_proj"):
+            self._parameters.pop(name, None)
+        for name in self._FP8_BUFFERS:
+            dt = torch.float8_e4m3fn if name.endswith("codes") else torch.float32
+            self.register_buffer(name, torch.zeros(0, dtype=dt))
+        return self
+
+    def load_fp8(self, w13: torch.Tensor, w2: torch.Tensor):
+        """Quantise this layer's stacked weights ([E, 2I, H], [E, H, I]) expert by expert and keep only the codes."""
+        from ..ops.moe import quantize_experts
+        if not self.fp8:
+            self.drop_bf16()
+        self.gate_up_codes, self.gate_up_scale, self.down_codes, self.down_scale = quantize_experts(w13, w2)
+        return self
+
+    def quantize_fp8_(self):
+        """In place, from the bf16 Parameters this module holds (``random:`` presets); they are freed."""
+        w13, w2 = self.gate_up_proj.detach(), self.down_proj.detach()
+        return self.load_fp8(w13, w2)
+
+    def _apply(self, fn, recurse=True):
+        """Moves follow the module; dtype casts (``model.to(torch.bfloat16)``) leave the codes and fp32 scales alone."""
+        if not self.fp8:
+            return super()._apply(fn, recurse)
+        keep = {n: getattr(self, n) for n in self._FP8_BUFFERS}
+        super()._apply(fn, recurse)
+        for n, t in keep.items():
+            if t.device.type != "meta":          # to_empty of a meta module: the applied (empty) buffer stands
+                setattr(self, n, t.to(getattr(self, n).device))
+        return self
 
 
 class Qwen3MoeBlock(nn.Module):
@@ -363,7 +406,11 @@ class Qwen3MoeBlock(nn.Module):
 
     def forward(self, x, residual=None):
         w, idx = moe_route(self.gate(x), self.top_k, self.routing)
-        return moe_experts(x, self.experts.gate_up_proj, self.experts.down_proj, idx, w, residual)
+        ex = self.experts
+        if ex.fp8:
+            return moe_experts_fp8(x, ex.gate_up_codes, ex.gate_up_scale, ex.down_codes, ex.down_scale, idx, w,
+                                   residual)
+        return moe_experts(x, ex.gate_up_proj, ex.down_proj, idx, w, residual)
 
 
 class Qwen3DecoderLayer(nn.Module):
@@ -570,11 +617,53 @@ class Qwen3ForCausalLM(nn.Module):
         from ..infer.generate import generate
         return generate(self, input_ids, attention_mask, generation_config, streamer=streamer, **kw)
 
+    # -------------------------------------------------------------- FP8 experts
+    def _moe_experts(self):
+        return [l.mlp.experts for l in self.model.layers if isinstance(l.mlp, Qwen3MoeBlock)]
+
+    def quantize_experts_fp8(self):
+        """Weight-only FP8 (e4m3) experts in place, layer by layer: each layer's bf16 expert Parameters are freed
+        before the next layer is quantised.  The router and everything else stay as they are."""
+        if not self._moe_experts():
+            raise ValueError("--moe-expert-dtype fp8: the model has no experts (not a Qwen3-MoE model)")
+        for ex in self._moe_experts():
+            if not ex.fp8:
+                ex.quantize_fp8_()
+        return self
+
+    def _fill_fp8_experts(self, keys, get) -> tuple:
+        """Quantise the expert tensors of every FP8-expert layer as that layer is filled: ``keys`` are the names
+        the checkpoint holds, ``get(name)`` hands one tensor over.  One layer's experts at a time are moved to
+        the device in bf16, stacked, quantised and dropped.  Returns the state-dict prefixes that were filled."""
+        E, done = self.config.num_experts, []
+        for i, layer in enumerate(self.model.layers):
+            ex = getattr(layer.mlp, "experts", None)
+            if ex is None or not ex.fp8:
+                continue
+            pre, dev = f"model.layers.{i}.mlp.experts.", layer.mlp.gate.weight.device
+            to = lambda name: get(name).to(dev, torch.bfloat16)     # noqa: E731
+            if pre + "gate_up_proj" in keys:                         # stacked (transformers >= 5)
+                w13, w2 = to(pre + "gate_up_proj"), to(pre + "down_proj")
+            elif f"{pre}0.gate_proj.weight" in keys:                 # per expert (the published checkpoints)
+                w13 = torch.stack([torch.cat([to(f"{pre}{j}.gate_proj.weight"), to(f"{pre}{j}.up_proj.weight")], 0)
+                                   for j in range(E)])
+                w2 = torch.stack([to(f"{pre}{j}.down_proj.weight") for j in range(E)])
+            else:
+                continue
+            ex.load_fp8(w13, w2)
+            del w13, w2
+            done.append(pre)
+        return tuple(done)
+
     # -------------------------------------------------------------- checkpoint IO
     def load_hf_state_dict(self, sd: dict[str, torch.Tensor], strict: bool = False):
         """Expert weights are taken stacked (``mlp.experts.gate_up_proj`` / ``down_proj``, transformers >= 5) or
         per expert (``mlp.experts.J.{gate,up,down}_proj.weight``, the published checkpoints)."""
-        own = self.state_dict()
+        filled = ()
+        if any(ex.fp8 for ex in self._moe_experts()):
+            sd = dict(sd)
+            filled = self._fill_fp8_experts(set(sd), sd.pop)
+        own = {k: v for k, v in self.state_dict().items() if not k.startswith(filled)} if filled else self.state_dict()
         if self.config.num_experts > 0 and any(".mlp.experts.0." in k for k in sd):
             sd = dict(sd)
             E = self.config.num_experts
@@ -597,25 +686,44 @@ class Qwen3ForCausalLM(nn.Module):
 
     @classmethod
     def from_pretrained(cls, path: str, dtype=torch.bfloat16, device=None, quantization_config=None,
-                        rope_scaling="keep", **_) -> "Qwen3ForCausalLM":
+                        rope_scaling="keep", moe_expert_dtype=None, **_) -> "Qwen3ForCausalLM":
         """Load ``config.json`` + ``*.safetensors`` shards from a local HF-layout dir.
         ``quantization_config`` (``BitsAndBytesConfig``-like, ``load_in_4bit``) quantises each
-        linear to NF4 as it is loaded (on the GPU kernel when ``device`` is cuda)."""
+        linear to NF4 as it is loaded (on the GPU kernel when ``device`` is cuda).
+        ``moe_expert_dtype`` ``"fp8"``: the expert tensors never become bf16 Parameters; they are read from the
+        shards one layer at a time and quantised to e4m3 codes as that layer is filled."""
         from safetensors import safe_open
         cfg = Qwen3Config.from_pretrained(path)
         if rope_scaling != "keep":
             cfg.rope_scaling = rope_scaling          # E7 passes rope_scaling=None
         with torch.device("meta"):
             m = cls(cfg)
+        fp8_experts = normalize_moe_expert_dtype(moe_expert_dtype) == "fp8"
+        if fp8_experts:
+            if not m._moe_experts():
+                raise ValueError(f"--moe-expert-dtype fp8: {path} has no experts (not a Qwen3-MoE model)")
+            for ex in m._moe_experts():
+                ex.drop_bf16()
         m.to_empty(device=device or "cpu")
         m.to(dtype)
         files = sorted(f for f in os.listdir(path) if f.endswith(".safetensors"))
-        sd = {}
+        sd, where = {}, {}
         for f in files:
             with safe_open(os.path.join(path, f), framework="pt", device="cpu") as fh:
                 for k in fh.keys():
-                    sd[k] = fh.get_tensor(k)
+                    if fp8_experts and ".mlp.experts." in k:
+                        where[k] = f                 # read when its layer is quantised
+                    else:
+                        sd[k] = fh.get_tensor(k)
         m.load_hf_state_dict(sd)
+        if fp8_experts:
+            handles = {}
+
+            def get(k):
+                if where[k] not in handles:
+                    handles[where[k]] = safe_open(os.path.join(path, where[k]), framework="pt", device="cpu")
+                return handles[where[k]].get_tensor(k)
+            m._fill_fp8_experts(where.keys(), get)
         inv, af = ref.rope_inv_freq(cfg.head_dim, cfg.rope_theta, cfg.rope_scaling)
         m.model.inv_freq = inv.to(device or "cpu")
         m.model.attn_factor = af
@@ -629,6 +737,9 @@ class Qwen3ForCausalLM(nn.Module):
 
     def save_pretrained(self, path: str, max_shard_bytes: int = 4 << 30):
         from safetensors.torch import save_file
+        if any(ex.fp8 for ex in self._moe_experts()):
+            raise ValueError("save_pretrained: FP8 experts are not saved; save the bf16 model and quantise at load "
+                             "(--moe-expert-dtype fp8)")
         os.makedirs(path, exist_ok=True)
         sd = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()
               if "inv_freq" not in k}

@@ -16,6 +16,12 @@ SwiGLU experts with stacked weights (Qwen3-MoE) run the whole expert MLP in two 
 (``moe_gemm.hip``) with nothing read back to the host, so a decode step stays graph-capturable:
 
     out = moe_experts(x, w13, w2, idx, w, base)    # dispatch → gemm_swiglu → gemm_down → combine
+
+Weight-only FP8 experts (e4m3 codes + one fp32 scale per expert row, bf16 activations) run the same four launches
+over the codes:
+
+    c13, s13, c2, s2 = quantize_experts(w13, w2)
+    out = moe_experts_fp8(x, c13, s13, c2, s2, idx, w, base)
 """
 from __future__ import annotations
 
@@ -204,4 +210,80 @@ def moe_experts(x, w13, w2, idx, w, base=None, row_class: int = 0):
     d = moe_dispatch(idx, w13.shape[0])
     hs = moe_gemm_swiglu(x, d, w13, row_class)
     ys = moe_gemm_down(hs, d, w2, row_class)
+    return moe_combine(ys, d, w, base)
+
+
+# ------------------------------------------------------------------ FP8 (e4m3) expert weights, W8A16
+def quantize_experts(w13, w2):
+    """Stacked expert weights → ``(c13, s13, c2, s2)``: e4m3 codes of the same shapes and one fp32 scale per
+    (expert, output row), by ``quant.fp8.quantize_rows`` on each expert's ``[rows, K]`` matrix in turn (the
+    transient is one expert)."""
+    from ..quant.fp8 import quantize_rows
+    out = []
+    for wt in (w13, w2):
+        E, R, K = wt.shape
+        codes = torch.empty(E, R, K, dtype=torch.float8_e4m3fn, device=wt.device)
+        scale = torch.empty(E, R, dtype=torch.float32, device=wt.device)
+        for e in range(E):
+            codes[e], scale[e] = quantize_rows(wt[e].detach())
+        out += [codes, scale]
+    return tuple(out)
+
+
+def moe_experts_fp8_reference(x, c13, s13, c2, s2, idx, w, base=None):
+    """``moe_experts_reference`` with weight-only FP8 experts: ``c13`` e4m3 [E, 2I, H] with ``s13`` fp32 [E, 2I],
+    ``c2`` [E, H, I] with ``s2`` [E, H].  The exact code values are multiplied and summed, and the row scale
+    multiplies the unrounded sum: g = (Σ_k x·val(c13[e, n]))·s13[e, n], likewise u with row I + n;
+    h = round(silu(g)·u); y = round((Σ_i h·val(c2[e, n]))·s2[e, n]); the combine is unchanged.  No weight is
+    rounded a second time.  fp64 ``x`` computes in fp64 throughout (the tests' oracle)."""
+    T, k = idx.shape
+    I = c2.shape[2]
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    flat = idx.reshape(-1)
+    tok = torch.arange(T * k, device=x.device) // k
+    ys = torch.zeros(T * k, x.shape[1], dtype=x.dtype, device=x.device)
+    for e in torch.unique(flat).tolist():
+        rows = (flat == e).nonzero().squeeze(1)
+        gu = (x[tok[rows]].to(acc) @ c13[e].to(acc).t()) * s13[e].to(acc)
+        h = (F.silu(gu[:, :I]) * gu[:, I:]).to(x.dtype)
+        ys = ys.index_copy(0, rows, ((h.to(acc) @ c2[e].to(acc).t()) * s2[e].to(acc)).to(x.dtype))
+    out = torch.zeros(T, x.shape[1], dtype=acc, device=x.device) if base is None else base.to(acc)
+    ys = ys.view(T, k, -1)
+    for j in range(k):
+        out = out + w[:, j:j + 1].to(acc) * ys[:, j].to(acc)
+    return out.to(x.dtype)
+
+
+def moe_gemm_fp8_supported(x, c13, s13, c2, s2) -> bool:
+    """What the FP8-weight grouped kernels serve: bf16 x, e4m3 codes with fp32 row scales, E <= 128,
+    H % 64 == 0, I % 64 == 0, contiguous and 16-byte aligned."""
+    if c13.dim() != 3 or c2.dim() != 3:
+        return False
+    E, I2, H = c13.shape
+    ok = (x.dtype == torch.bfloat16 and x.dim() == 2 and c13.dtype == c2.dtype == torch.float8_e4m3fn
+          and s13.dtype == s2.dtype == torch.float32 and E <= 128 and H % 64 == 0 and I2 % 128 == 0
+          and tuple(c2.shape) == (E, H, I2 // 2) and tuple(s13.shape) == (E, I2) and tuple(s2.shape) == (E, H))
+    return ok and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (c13, s13, c2, s2))
+
+
+def moe_gemm_swiglu_fp8(x, d: Dispatch, c13, s13, row_class: int = 0):
+    """``moe_gemm_swiglu`` over e4m3 codes: the row scales meet the fp32 sums of g and u before SwiGLU."""
+    return native().moe_gemm_swiglu_fp8(x.contiguous(), d.perm, d.offsets, c13, s13, d.k, row_class)
+
+
+def moe_gemm_down_fp8(hs, d: Dispatch, c2, s2, row_class: int = 0):
+    """``moe_gemm_down`` over e4m3 codes: row p = bf16((hs[p] · val(c2[e])ᵀ) · s2[e])."""
+    return native().moe_gemm_down_fp8(hs, d.offsets, c2, s2, row_class)
+
+
+def moe_experts_fp8(x, c13, s13, c2, s2, idx, w, base=None, row_class: int = 0):
+    """``moe_experts`` with weight-only FP8 experts (see ``moe_experts_fp8_reference``): dispatch, the two FP8
+    grouped launches and the unchanged combine, with no host read of the routing.  CPU tensors,
+    ``LIPA_REFERENCE=1``, unsupported shapes and inputs that require grad run the reference."""
+    grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, base))
+    if not use_native(x) or grad or not moe_gemm_fp8_supported(x, c13, s13, c2, s2) or idx.numel() == 0:
+        return moe_experts_fp8_reference(x, c13, s13, c2, s2, idx, w, base)
+    d = moe_dispatch(idx, c13.shape[0])
+    hs = moe_gemm_swiglu_fp8(x, d, c13, s13, row_class)
+    ys = moe_gemm_down_fp8(hs, d, c2, s2, row_class)
     return moe_combine(ys, d, w, base)

@@ -50,13 +50,67 @@ def timed(fn, iters):
     return a.elapsed_time(b) / iters * 1e3      # µs per call
 
 
+def main_fp8(a):
+    """``--fp8``: ``moe_experts`` (bf16 experts) against ``moe_experts_fp8`` (e4m3 codes of the same weights), interleaved
+    round by round.  Live-expert weight bytes (3·H·I·{2, 1} per distinct expert, the fp32 scales included for FP8) over
+    the whole op's time are given for both; a ratio above 1 (FP8 slower) is marked with ``**``."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    w13 = (torch.randn(E, 2 * I, H, device=dev, generator=g) * H ** -0.5).bfloat16()
+    w2 = (torch.randn(E, H, I, device=dev, generator=g) * I ** -0.5).bfloat16()
+    q = moe.quantize_experts(w13, w2)
+    lines = [f"routed expert MLP, E {E} top-{K} H {H} I {I}, bf16 experts / FP8 (e4m3, W8A16) experts; {ROUNDS} rounds x "
+             f">= {ITERS} calls (>= 50 ms), interleaved, {NROUTE} uniform routings in turn",
+             f"{'T':>5} {'class':>6} | {'bf16 us (min..max)':>30} | {'fp8 us (min..max)':>30} | {'fp8/bf16':>10} | "
+             f"live experts, weight GB/s bf16, fp8"]
+    for T in a.tokens:
+        x = torch.randn(T, H, device=dev, generator=g).bfloat16()
+        routes = []
+        for _ in range(NROUTE):
+            idx = torch.rand(T, E, device=dev, generator=g).topk(K, -1).indices
+            routes.append((idx, torch.rand(T, K, device=dev, generator=g)))
+        live = statistics.mean(len(torch.unique(idx)) for idx, _ in routes)
+        fns = {"bf16": lambda i: moe.moe_experts(x, w13, w2, *routes[i % NROUTE]),
+               "fp8": lambda i: moe.moe_experts_fp8(x, *q, *routes[i % NROUTE])}
+        ref = moe.moe_experts_fp8_reference(x, *q, *routes[0])
+        diff = (ref.float() - fns["fp8"](0).float()).abs().max().item()
+        for fn in fns.values():
+            for i in range(NROUTE):
+                fn(i)
+        torch.cuda.synchronize()
+        iters = max(ITERS, min(1000, int(5e4 / timed(fns["bf16"], ITERS))))
+        t = {"bf16": [], "fp8": []}
+        for _ in range(ROUNDS):
+            for name, fn in fns.items():
+                t[name].append(timed(fn, iters))
+        med = {n: statistics.median(v) for n, v in t.items()}
+        cell = {n: f"{med[n]:9.1f} ({min(t[n]):.1f}..{max(t[n]):.1f})" for n in t}
+        cls = "skinny" if native().moe_gemm_class(T * K, E) == 1 else "tiled"
+        ratio = med["fp8"] / med["bf16"]
+        gbs = (f"{live:6.1f}, {live * 3 * H * I * 2 / med['bf16'] / 1e3:6.0f}, "
+               f"{live * (3 * H * I + 4 * (2 * I + H)) / med['fp8'] / 1e3:6.0f}")
+        lines.append(f"{T:>5} {cls:>6} | {cell['bf16']:>30} | {cell['fp8']:>30} | "
+                     f"{('**%.3f**' if ratio > 1 else '%.3f') % ratio:>10} | {gbs}   (max |reference - fp8| {diff:.2e})")
+        print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--tokens", type=int, nargs="+", default=[1, 8, 64, 256, 2048])
+    ap.add_argument("--fp8", action="store_true", help="bf16 experts against FP8 (e4m3) experts instead of loop / grouped")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe_gemm: needs the GPU (no CPU fall-back for a timing)")
+    if a.fp8:
+        text = "\n".join(main_fp8(a)) + "\n"
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        print(text)
+        return
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
     w13 = (torch.randn(E, 2 * I, H, device=dev, generator=g) * H ** -0.5).bfloat16()

@@ -101,8 +101,9 @@ void launch_moe_gather(int, const void*, const int*, const float*, void*, int, i
 void launch_moe_combine(int, const void*, const int*, const float*, const void*, void*, int, int, int, hipStream_t);
 void launch_moe_wgrad(int, const void*, const void*, const int*, float*, int, int, int, hipStream_t);
 int moe_gemm_class(int, int);
-void launch_moe_gemm(int, int, const void*, const int*, int, const int*, const void*, void*, int, int, int, int,
+void launch_moe_gemm(int, int, const void*, const int*, int, const int*, const void*, void*, void*, int, int, int, int,
                      hipStream_t);
+void launch_moe_gemm_bwd(int, const void*, const int*, const void*, const void*, void*, int, int, int, int, hipStream_t);
 void launch_moe_gemm_fp8(int, int, const void*, const int*, int, const int*, const void*, const float*, void*, int, int,
                          int, int, hipStream_t);
 int lora_acc_chunks(int M, int K);
@@ -2216,7 +2217,9 @@ void moe_gemm_check(const char* who, const Tensor& a, const Tensor& offsets, con
 }
 }  // namespace
 
-Tensor moe_gemm_swiglu(Tensor x, Tensor perm, Tensor offsets, Tensor w13, int64_t k, int64_t row_class) {
+// gu (optional, written): bf16 [T*k, 2I], the rounded g and u of every row, saved for moe_gemm_dswiglu
+Tensor moe_gemm_swiglu(Tensor x, Tensor perm, Tensor offsets, Tensor w13, int64_t k, int64_t row_class,
+                       optional<Tensor> gu) {
   CHECK_CONTIG(x); CHECK_CONTIG(perm); CHECK_CONTIG(w13);
   TORCH_CHECK(x.dim() == 2 && w13.dim() == 3 && w13.size(2) == x.size(1) && w13.size(1) % 2 == 0,
               "moe_gemm_swiglu: x [T, H], w13 [E, 2I, H]");
@@ -2225,9 +2228,13 @@ Tensor moe_gemm_swiglu(Tensor x, Tensor perm, Tensor offsets, Tensor w13, int64_
   TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == at::kInt && k >= 1 && perm.numel() == x.size(0) * k &&
               perm.numel() < (1 << 24), "moe_gemm_swiglu: perm int32 [T*k]");
   const int P = perm.numel(), E = w13.size(0);
+  if (gu.has_value())
+    TORCH_CHECK(gu->is_cuda() && gu->is_contiguous() && gu->scalar_type() == at::kBFloat16 && gu->dim() == 2 &&
+                gu->size(0) == P && gu->size(1) == 2 * I, "moe_gemm_swiglu: gu bf16 [T*k, 2I]");
   Tensor hs = torch::empty({P, I}, x.options());
   if (P) launch_moe_gemm(0, moe_gemm_pick(row_class, P, E), x.data_ptr(), perm.data_ptr<int>(), (int)k,
-                         offsets.data_ptr<int>(), w13.data_ptr(), hs.data_ptr(), P, E, (int)I, (int)H, stream());
+                         offsets.data_ptr<int>(), w13.data_ptr(), hs.data_ptr(),
+                         gu.has_value() ? gu->data_ptr() : nullptr, P, E, (int)I, (int)H, stream());
   return hs;
 }
 
@@ -2240,8 +2247,40 @@ Tensor moe_gemm_down(Tensor hs, Tensor offsets, Tensor w2, int64_t row_class) {
   const int P = hs.size(0), E = w2.size(0);
   Tensor ys = torch::empty({P, H}, hs.options());
   if (P) launch_moe_gemm(1, moe_gemm_pick(row_class, P, E), hs.data_ptr(), nullptr, 1, offsets.data_ptr<int>(),
-                         w2.data_ptr(), ys.data_ptr(), P, E, (int)H, (int)I, stream());
+                         w2.data_ptr(), ys.data_ptr(), nullptr, P, E, (int)H, (int)I, stream());
   return ys;
+}
+
+// ---- their input gradients for frozen experts (moe_gemm_nn_k): the checkpoint layouts are read as they are
+// dgu [P, 2I] = dSwiGLU(dys · w2[e]; gu): dys [P, H], gu [P, 2I] from moe_gemm_swiglu, w2 [E, H, I]
+Tensor moe_gemm_dswiglu(Tensor dys, Tensor gu, Tensor offsets, Tensor w2) {
+  CHECK_CONTIG(dys); CHECK_CONTIG(gu); CHECK_CONTIG(w2);
+  TORCH_CHECK(dys.dim() == 2 && gu.dim() == 2 && w2.dim() == 3 && w2.size(1) == dys.size(1) &&
+              gu.size(0) == dys.size(0) && gu.size(1) == 2 * w2.size(2), "moe_gemm_dswiglu: dys [P, H], gu [P, 2I], w2 [E, H, I]");
+  const int64_t H = w2.size(1), I = w2.size(2);
+  moe_gemm_check("moe_gemm_dswiglu", dys, offsets, w2, H, I);
+  TORCH_CHECK(gu.is_cuda() && gu.scalar_type() == at::kBFloat16, "moe_gemm_dswiglu: gu bf16 on the device");
+  TORCH_CHECK(dys.size(0) < (1 << 24), "moe_gemm_dswiglu: < 2^24 rows");
+  const int P = dys.size(0), E = w2.size(0);
+  Tensor dgu = torch::empty({P, 2 * I}, dys.options());
+  if (P) launch_moe_gemm_bwd(0, dys.data_ptr(), offsets.data_ptr<int>(), w2.data_ptr(), gu.data_ptr(), dgu.data_ptr(), P,
+                             E, (int)I, (int)H, stream());
+  return dgu;
+}
+
+// dxs [P, H] = dgu · w13[e]: dgu [P, 2I], w13 [E, 2I, H]
+Tensor moe_gemm_dx(Tensor dgu, Tensor offsets, Tensor w13) {
+  CHECK_CONTIG(dgu); CHECK_CONTIG(w13);
+  TORCH_CHECK(dgu.dim() == 2 && w13.dim() == 3 && w13.size(1) == dgu.size(1) && w13.size(1) % 2 == 0,
+              "moe_gemm_dx: dgu [P, 2I], w13 [E, 2I, H]");
+  const int64_t H = w13.size(2), I = w13.size(1) / 2;
+  moe_gemm_check("moe_gemm_dx", dgu, offsets, w13, H, I);
+  TORCH_CHECK(dgu.size(0) < (1 << 24), "moe_gemm_dx: < 2^24 rows");
+  const int P = dgu.size(0), E = w13.size(0);
+  Tensor dxs = torch::empty({P, H}, dgu.options());
+  if (P) launch_moe_gemm_bwd(1, dgu.data_ptr(), offsets.data_ptr<int>(), w13.data_ptr(), nullptr, dxs.data_ptr(), P, E,
+                             (int)H, (int)(2 * I), stream());
+  return dxs;
 }
 
 // ---- the same two stages over e4m3 expert weights: codes [E, NW, K] + fp32 scale [E, NW] (W8A16, moe_gemm.hip)
@@ -2354,7 +2393,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_combine", &moe_combine);
   m.def("moe_wgrad", &moe_wgrad);
   m.def("moe_gemm_swiglu", &moe_gemm_swiglu, py::arg("x"), py::arg("perm"), py::arg("offsets"), py::arg("w13"),
-        py::arg("k"), py::arg("row_class") = 0);
+        py::arg("k"), py::arg("row_class") = 0, py::arg("gu") = py::none());
+  m.def("moe_gemm_dswiglu", &moe_gemm_dswiglu, py::arg("dys"), py::arg("gu"), py::arg("offsets"), py::arg("w2"));
+  m.def("moe_gemm_dx", &moe_gemm_dx, py::arg("dgu"), py::arg("offsets"), py::arg("w13"));
   m.def("moe_gemm_down", &moe_gemm_down, py::arg("hs"), py::arg("offsets"), py::arg("w2"), py::arg("row_class") = 0);
   m.def("moe_gemm_swiglu_fp8", &moe_gemm_swiglu_fp8, py::arg("x"), py::arg("perm"), py::arg("offsets"),
         py::arg("c13"), py::arg("s13"), py::arg("k"), py::arg("row_class") = 0);

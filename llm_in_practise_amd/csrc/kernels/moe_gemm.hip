@@ -46,6 +46,32 @@
 //    bytes) goes global → registers one stage ahead, is converted ONCE per workgroup (two 16-byte loads, two cvt16
 //    and four ds_write_b128 per thread) and is written as the same swizzled bf16 image; fragment reads and the
 //    MFMA loop are those of the bf16 kernel.  The gathered x rows keep going by LDS-DMA.
+//
+// Backward with frozen experts (moe_gemm_nn_k; fine-tuning with adapters elsewhere, base weights frozen).  Under
+// autograd the SwiGLU stage also writes gu [P, 2I] = bf16(g), bf16(u) from the same epilogue (template parameter GU;
+// hs still comes from the unrounded accumulators, so the forward bits do not change), and the input gradient is two
+// launches of one NN kernel, out[p, n] = Σ_k A[p, k] · W[e][k][n] with W row-major in n, i.e. the checkpoint layouts
+// w2 [E, H, I] and w13 [E, 2I, H] read as they are:
+//
+//   dswiglu: dh = dys[p] · w2[e] (K = H, N = I), never stored; with s = 1 / (1 + exp(-g)):
+//            dgu[p, n] = bf16(dh·u·s·(1 + g·(1 - s))),  dgu[p, I + n] = bf16(dh·g·s)
+//   dx:      dxs[p, n] = bf16(dgu[p] · w13[e]) (K = 2I, N = H); moe_combine then sums a token's k rows.
+//
+// One tiled class for every P: the forward's 64-row × 128-column tiles, BK = 64, 2 × 2 waves, grid and find_tile scan,
+// LDS-DMA double buffering with one barrier per stage, K ascending into one accumulator, no atomics, no split-K, and
+// the same row invariance (a dxs row depends on its dys and gu rows and its expert's weights only).  What differs is
+// the W stage: 64 k-rows × 128 columns (256 B per k-row, 16 KiB), so a wave DMA instruction fills 4 k-rows.  The MFMA
+// keeps the weight fragment as its A operand, which wants 8 consecutive k at a fixed n per lane; the image has n
+// contiguous, so a fragment is two ds_read_b64_tr_b16: lane (g, kq, kp) of a k-step reads 8 bytes of k-row 8g + kq
+// (then + 4) at columns 4·kp .. + 3 of the fragment's 32-B column pair, and receives k-rows 8g .. 8g + 3 (+ 4) of
+// column li.  Swizzle: pair c of k-row k sits at pair c ^ h(k), h(k) = (k & 3) | ((k >> 1) & 4), applied on the global
+// source address (slot ch of a DMA'd k-row ← 16-B chunk ch ^ 2·h(k), which keeps a pair's halves in place).  Why it
+// is conflict-free: LDS serves a 64-bit wave read in two halves of 32 lanes; a half is g ∈ {2m, 2m + 1}, kq ∈ 0..3,
+// i.e. the 8 k-rows {16m .. 16m + 3, 16m + 8 .. 16m + 11} (+ 4 for the second read), 32 contiguous bytes each.  Every
+// k-row starts on bank 0 (256-B rows, 64 banks × 4 B), so unswizzled all 8 would hit the same 8 banks; h takes the 8
+// values kq | 4·(g & 1) on them, so the 8 rows land in 8 distinct 32-B bank slots and cover the 64 banks once.  The
+// DMA's own writes are 1 KiB contiguous whatever the source.  K is never ragged (H % 64 == 2I % 64 == 0); ragged N
+// (I or H not a multiple of 128) is clamped per 16-B chunk on load and masked on store.
 #include "common.h"
 
 using namespace lipa;
@@ -66,11 +92,18 @@ __device__ __forceinline__ void store4(bf16* p, float a, float b, float c, float
 }
 
 // Epilogue shared by both classes.  acc[j] holds C[n = nrow[j] + 4g + i][row]; SWIGLU: j = 0 gate, j = 1 up of
-// the same logical columns → one 8-byte store; DOWN: one 8-byte store per fragment.
-template <bool SWIGLU>
+// the same logical columns → one 8-byte store; DOWN: one 8-byte store per fragment.  GU (SWIGLU under autograd): g and
+// u themselves, the fp32 accumulators rounded once, also go to gu [P, 2·ldo] (g in columns 0..I-1, u in I..2I-1);
+// hs is still computed from the unrounded accumulators.
+template <bool SWIGLU, bool GU = false>
 __device__ __forceinline__ void store_pair(bf16* out, int ldo, int p, int col0, int col1, const f32x4& a0,
-                                           const f32x4& a1) {
+                                           const f32x4& a1, bf16* gu = nullptr) {
   bf16* o = out + (size_t)p * ldo;
+  if (GU) {
+    bf16* q = gu + (size_t)p * 2 * ldo + col0;
+    store4(q, a0[0], a0[1], a0[2], a0[3]);
+    store4(q + ldo, a1[0], a1[1], a1[2], a1[3]);
+  }
   if (SWIGLU) {
     store4(o + col0, silu_mul(a0[0], a1[0]), silu_mul(a0[1], a1[1]), silu_mul(a0[2], a1[2]), silu_mul(a0[3], a1[3]));
   } else {
@@ -81,10 +114,11 @@ __device__ __forceinline__ void store_pair(bf16* out, int ldo, int p, int col0, 
 
 // ------------------------------------------------------------------ skinny
 // One group of up to 16·MT rows [r0, r1) of the segment against this wave's two W fragments.
-template <bool SWIGLU, int MT>
+template <bool SWIGLU, bool GU, int MT>
 __device__ __forceinline__ void skinny_rows(const bf16* __restrict__ A, const int* __restrict__ perm, int kdiv,
-                                            const bf16* wr0, const bf16* wr1, bf16* __restrict__ out, int ldo, int K,
-                                            int r0, int r1, int col0, int col1) {
+                                            const bf16* wr0, const bf16* wr1, bf16* __restrict__ out,
+                                            bf16* __restrict__ gu, int ldo, int K, int r0, int r1, int col0,
+                                            int col1) {
   const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
   const bf16* xr[MT];
 #pragma unroll
@@ -120,17 +154,17 @@ __device__ __forceinline__ void skinny_rows(const bf16* __restrict__ A, const in
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
     const int p = r0 + 16 * mt + li;
-    if (p < r1) store_pair<SWIGLU>(out, ldo, p, col0 + 4 * g, col1 + 4 * g, acc[0][mt], acc[1][mt]);
+    if (p < r1) store_pair<SWIGLU, GU>(out, ldo, p, col0 + 4 * g, col1 + 4 * g, acc[0][mt], acc[1][mt], gu);
   }
 }
 
 // A [rows, K] (x through perm for SWIGLU, hs for DOWN); W [E, NW, K] with NW = 2N (SWIGLU) or N (DOWN);
-// out [P, N].  grid = E · ceil(N / (SWIGLU ? 64 : 128)).
-template <bool SWIGLU>
+// out [P, N]; GU: gu [P, 2N] as well.  grid = E · ceil(N / (SWIGLU ? 64 : 128)).
+template <bool SWIGLU, bool GU = false>
 __global__ __launch_bounds__(256) void moe_gemm_skinny_k(const bf16* __restrict__ A, const int* __restrict__ perm,
                                                          int kdiv, const int* __restrict__ offsets,
-                                                         const bf16* __restrict__ W, bf16* __restrict__ out, int N,
-                                                         int K, int nblk) {
+                                                         const bf16* __restrict__ W, bf16* __restrict__ out,
+                                                         bf16* __restrict__ gu, int N, int K, int nblk) {
   const int e = blockIdx.x / nblk, bn = blockIdx.x % nblk;
   const int s0 = offsets[e], s1 = offsets[e + 1];
   if (s1 <= s0) return;
@@ -144,9 +178,9 @@ __global__ __launch_bounds__(256) void moe_gemm_skinny_k(const bf16* __restrict_
   const bf16* wr1 = We + (size_t)((SWIGLU ? N + col0 : col1) + li) * K + 8 * g;
   for (int r0 = s0; r0 < s1; r0 += 64) {
     const int r1 = min(s1, r0 + 64), n = r1 - r0;
-    if (n <= 16) skinny_rows<SWIGLU, 1>(A, perm, kdiv, wr0, wr1, out, N, K, r0, r1, col0, col1);
-    else if (n <= 32) skinny_rows<SWIGLU, 2>(A, perm, kdiv, wr0, wr1, out, N, K, r0, r1, col0, col1);
-    else skinny_rows<SWIGLU, 4>(A, perm, kdiv, wr0, wr1, out, N, K, r0, r1, col0, col1);
+    if (n <= 16) skinny_rows<SWIGLU, GU, 1>(A, perm, kdiv, wr0, wr1, out, gu, N, K, r0, r1, col0, col1);
+    else if (n <= 32) skinny_rows<SWIGLU, GU, 2>(A, perm, kdiv, wr0, wr1, out, gu, N, K, r0, r1, col0, col1);
+    else skinny_rows<SWIGLU, GU, 4>(A, perm, kdiv, wr0, wr1, out, gu, N, K, r0, r1, col0, col1);
   }
 }
 
@@ -187,11 +221,11 @@ __device__ __forceinline__ bool find_tile(const int* __restrict__ offsets, int E
   return true;
 }
 
-template <bool SWIGLU>
+template <bool SWIGLU, bool GU = false>
 __global__ __launch_bounds__(256) void moe_gemm_tiled_k(const bf16* __restrict__ A, const int* __restrict__ perm,
                                                         int kdiv, const int* __restrict__ offsets,
-                                                        const bf16* __restrict__ W, bf16* __restrict__ out, int E,
-                                                        int N, int K, int nblk) {
+                                                        const bf16* __restrict__ W, bf16* __restrict__ out,
+                                                        bf16* __restrict__ gu, int E, int N, int K, int nblk) {
   __shared__ __attribute__((aligned(16))) bf16 sx[2][MG_BM * MG_BK];
   __shared__ __attribute__((aligned(16))) bf16 sw[2][MG_BN * MG_BK];
   int e, r0, s1;
@@ -282,7 +316,128 @@ __global__ __launch_bounds__(256) void moe_gemm_tiled_k(const bf16* __restrict__
       // SWIGLU: fragments (2c, 2c+1) = gate / up of columns wn·32 + 16c; DOWN: columns wn·64 + 32c (+16)
       const int col0 = bn * cols + (SWIGLU ? wn * 32 + 16 * c : wn * 64 + 32 * c) + 4 * g;
       if (col0 >= N) continue;
-      store_pair<SWIGLU>(out, N, p, col0, col0 + 16, acc[2 * c][mi], acc[2 * c + 1][mi]);
+      store_pair<SWIGLU, GU>(out, N, p, col0, col0 + 16, acc[2 * c][mi], acc[2 * c + 1][mi], gu);
+    }
+  }
+}
+
+// ================================================================== backward with frozen experts: NN grouped GEMMs
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+
+// W image swizzle: the 32-B column pair c of k-row k sits at pair c ^ nn_swz(k) of the row's 8 pairs
+__device__ __forceinline__ int nn_swz(int k) { return (k & 3) | ((k >> 1) & 4); }
+
+// out[p, n] = Σ_k A[p, k] · W[e][k][n] for p in expert e's segment: A [P, K], W [E, K, N] with n contiguous.
+//   DSWIGLU (A = dys, W = w2, K = H, N = I): acc = dh, never stored; with g, u = gu[p, n], gu[p, N + n] and
+//     s = 1 / (1 + exp(-g)):  out[p, n] = bf16(dh·u·s·(1 + g·(1 - s))),  out[p, N + n] = bf16(dh·g·s);  out [P, 2N].
+//   else (A = dgu, W = w13, K = 2I, N = H): out[p, n] = bf16(acc);  out [P, N].
+// grid = (row tiles of find_tile) × ceil(N / 128); K % 64 == 0, N % 32 == 0.
+template <bool DSWIGLU>
+__global__ __launch_bounds__(256) void moe_gemm_nn_k(const bf16* __restrict__ A, const int* __restrict__ offsets,
+                                                     const bf16* __restrict__ W, const bf16* __restrict__ gu,
+                                                     bf16* __restrict__ out, int E, int N, int K, int nblk) {
+  __shared__ __attribute__((aligned(16))) bf16 sx[2][MG_BM * MG_BK];
+  __shared__ __attribute__((aligned(16))) bf16 sw[2][MG_BK * MG_BN];
+  int e, r0, s1;
+  if (!find_tile(offsets, E, blockIdx.x / nblk, e, r0, s1)) return;
+  const int n0 = (blockIdx.x % nblk) * MG_BN;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
+  const int wm = w >> 1, wn = w & 1;          // 2 × 2 waves: 32 rows × 64 output columns each
+  const bf16* We = W + (size_t)e * K * N;
+
+  // DMA sources.  A: as the forward (8 rows × 8 slots per wave instruction, slot s of row r ← chunk s ^ (r & 7)).
+  // W: a wave instruction fills 4 k-rows × 16 slots; slot ch of k-row kr ← 16-B chunk ch ^ 2·nn_swz(kr) of the
+  // workgroup's 128 columns, clamped into the row when N is ragged (those columns are masked on store).
+  const bf16* xsrc[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = (q * 4 + w) * 8 + (lane >> 3);
+    const int p = min(r0 + r, s1 - 1);
+    xsrc[q] = A + (size_t)p * K + 8 * ((lane & 7) ^ (r & 7));
+  }
+  const bf16* wsrc[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int kr = (q * 4 + w) * 4 + (lane >> 4);
+    const int cc = (lane & 15) ^ (2 * nn_swz(kr));
+    wsrc[q] = We + (size_t)kr * N + min(n0 + 8 * cc, N - 8);
+  }
+  auto issue = [&](int buf, int k0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) dma16(xsrc[q] + k0, &sx[buf][(q * 4 + w) * 8 * MG_BK]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dma16(wsrc[q] + (size_t)k0 * N, &sw[buf][(q * 4 + w) * 4 * MG_BN]);
+  };
+
+  // transposed fragment reads: lane (g, kq, kp) reads 8 bytes of k-row 8g + kq (and + 4), columns 4·kp .. + 3 of the
+  // fragment's pair; nn_swz of both rows, and of the rows 32 further on, is kq | 4·(g & 1)
+  const int kq = (lane >> 2) & 3, kp = lane & 3;
+  int woff[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) woff[j] = (8 * g + kq) * MG_BN + 16 * ((wn * 4 + j) ^ (kq | ((g & 1) << 2))) + 4 * kp;
+
+  f32x4 acc[4][2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) acc[j][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = K / MG_BK;
+  issue(0, 0);
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this lane's part of stage kt has landed
+    __syncthreads();                                        // stage kt visible; every wave is done reading stage kt-1
+    if (kt + 1 < nk) issue(buf ^ 1, (kt + 1) * MG_BK);      // flies under this stage's MFMAs
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int c = ks * 4 + g;
+      bf16x8 b[2], a[4];
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        const int r = wm * 32 + mi * 16 + li;
+        b[mi] = *reinterpret_cast<const bf16x8*>(&sx[buf][r * MG_BK + 8 * (c ^ (r & 7))]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bf16* pw = &sw[buf][ks * 32 * MG_BN + woff[j]];
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)pw);
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(pw + 4 * MG_BN));
+        a[j] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+          acc[j][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], b[mi], acc[j][mi], 0, 0, 0);
+    }
+  }
+
+  // acc[j][mi][i] = C[p = r0 + 32·wm + 16·mi + li][n = n0 + 64·wn + 16·j + 4·g + i]
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi) {
+    const int p = r0 + wm * 32 + mi * 16 + li;
+    if (p >= s1) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = n0 + wn * 64 + 16 * j + 4 * g;
+      if (col >= N) continue;                               // N % 4 == 0: a lane's four columns are in or out together
+      const f32x4& dh = acc[j][mi];
+      if (DSWIGLU) {
+        const size_t at = (size_t)p * 2 * N + col;
+        const bf16x4 gv = *reinterpret_cast<const bf16x4*>(gu + at), uv = *reinterpret_cast<const bf16x4*>(gu + at + N);
+        float dg[4], du[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float gg = (float)gv[i], uu = (float)uv[i], s = 1.f / (1.f + __expf(-gg));
+          dg[i] = dh[i] * uu * s * (1.f + gg * (1.f - s));
+          du[i] = dh[i] * gg * s;
+        }
+        store4(out + at, dg[0], dg[1], dg[2], dg[3]);
+        store4(out + at + N, du[0], du[1], du[2], du[3]);
+      } else {
+        store4(out + (size_t)p * N + col, dh[0], dh[1], dh[2], dh[3]);
+      }
     }
   }
 }
@@ -521,27 +676,40 @@ int moe_gemm_class(int P, int E) { return (long long)P <= 32LL * E ? 1 : 2; }
 
 // stage 0: A = x [T, K=H], perm [P], W = w13 [E, 2N, K], out = hs [P, N=I]
 // stage 1: A = hs [P, K=I], perm = nullptr, W = w2 [E, N=H, K], out = ys [P, N]
+// gu (stage 0 only, may be null): [P, 2N] bf16, the rounded g and u that the backward reads
 void launch_moe_gemm(int stage, int cls, const void* A, const int* perm, int kdiv, const int* offsets, const void* W,
-                     void* out, int P, int E, int N, int K, hipStream_t st) {
+                     void* out, void* gu, int P, int E, int N, int K, hipStream_t st) {
   const int nblk = stage == 0 ? (N + 63) / 64 : (N + 127) / 128;
+  const bf16 *a = (const bf16*)A, *wt = (const bf16*)W;
+  bf16 *o = (bf16*)out, *q = (bf16*)gu;
   if (cls == 1) {
     const int grid = E * nblk;
-    if (stage == 0)
-      moe_gemm_skinny_k<true><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out, N,
-                                                    K, nblk);
-    else
-      moe_gemm_skinny_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out,
-                                                     N, K, nblk);
+    if (stage == 0 && q) moe_gemm_skinny_k<true, true><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, wt, o, q, N, K, nblk);
+    else if (stage == 0) moe_gemm_skinny_k<true><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, wt, o, nullptr, N, K, nblk);
+    else moe_gemm_skinny_k<false><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, wt, o, nullptr, N, K, nblk);
   } else {
     const int tiles = P < P / MG_BM + E ? P : P / MG_BM + E;     // >= Σ_e ceil(c_e / BM) for every routing
     const int grid = tiles * nblk;
-    if (stage == 0)
-      moe_gemm_tiled_k<true><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out, E,
-                                                   N, K, nblk);
-    else
-      moe_gemm_tiled_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, (const bf16*)W, (bf16*)out, E,
-                                                    N, K, nblk);
+    if (stage == 0 && q) moe_gemm_tiled_k<true, true><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, wt, o, q, E, N, K, nblk);
+    else if (stage == 0) moe_gemm_tiled_k<true><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, wt, o, nullptr, E, N, K, nblk);
+    else moe_gemm_tiled_k<false><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, wt, o, nullptr, E, N, K, nblk);
   }
+  LIPA_CHECK_LAUNCH();
+}
+
+// Backward with frozen experts.  stage 0: A = dys [P, K=H], W = w2 [E, K, N=I], gu [P, 2N] → out = dgu [P, 2N];
+// stage 1: A = dgu [P, K=2I], W = w13 [E, K, N=H] → out = dxs [P, N].  One tiled class for every P.
+void launch_moe_gemm_bwd(int stage, const void* A, const int* offsets, const void* W, const void* gu, void* out, int P,
+                         int E, int N, int K, hipStream_t st) {
+  const int nblk = (N + MG_BN - 1) / MG_BN;
+  const int tiles = P < P / MG_BM + E ? P : P / MG_BM + E;
+  const int grid = tiles * nblk;
+  if (stage == 0)
+    moe_gemm_nn_k<true><<<grid, 256, 0, st>>>((const bf16*)A, offsets, (const bf16*)W, (const bf16*)gu, (bf16*)out, E,
+                                              N, K, nblk);
+  else
+    moe_gemm_nn_k<false><<<grid, 256, 0, st>>>((const bf16*)A, offsets, (const bf16*)W, nullptr, (bf16*)out, E, N, K,
+                                               nblk);
   LIPA_CHECK_LAUNCH();
 }
 

@@ -17,6 +17,9 @@ SwiGLU experts with stacked weights (Qwen3-MoE) run the whole expert MLP in two 
 
     out = moe_experts(x, w13, w2, idx, w, base)    # dispatch → gemm_swiglu → gemm_down → combine
 
+With frozen experts that call is differentiable in ``x``, ``w`` and ``base`` on the same kernels; the backward adds two
+grouped launches over the untransposed weights (``moe_gemm_dswiglu``, ``moe_gemm_dx``).
+
 Weight-only FP8 experts (e4m3 codes + one fp32 scale per expert row, bf16 activations) run the same four launches
 over the codes:
 
@@ -198,18 +201,76 @@ def moe_gemm_down(hs, d: Dispatch, w2, row_class: int = 0):
     return native().moe_gemm_down(hs, d.offsets, w2.contiguous(), row_class)
 
 
+def moe_experts_backward_reference(dout, x, w13, w2, idx, w):
+    """The per-pair specification of the backward of ``moe_experts`` with frozen experts, in torch: ``(dx, dw)``.
+
+    For each pair (t, j), e = idx[t, j], with g, u, y of ``moe_experts_reference``:
+    gu = round(g), round(u) (the fp32 sums rounded once; what the forward saves);  dw[t, j] = Σ_h dout[t, h]·y[h];
+    dy = round(w[t, j]·dout[t]);  dh = dy·w2[e] (fp32, never rounded);  with s = 1/(1 + exp(−g)) of the rounded g:
+    dg = round(dh·u·s·(1 + g·(1 − s))), du = round(dh·g·s);  dxs = round([dg, du]·w13[e]);
+    dx[t] = round(Σ_j dxs(t, j)) with the sum in fp32 in j order.  ``round`` is to x's dtype; fp64 ``x`` computes in
+    fp64 throughout.  dbase is dout."""
+    T, k = idx.shape
+    I = w2.shape[2]
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    dx = torch.zeros(T, x.shape[1], dtype=acc, device=x.device)
+    dw = torch.zeros(T, k, dtype=acc, device=x.device)
+    for j in range(k):
+        w13e, w2e = w13[idx[:, j]].to(acc), w2[idx[:, j]].to(acc)
+        gu32 = torch.einsum("th,tnh->tn", x.to(acc), w13e)
+        h = (F.silu(gu32[:, :I]) * gu32[:, I:]).to(x.dtype)
+        y = torch.einsum("ti,thi->th", h.to(acc), w2e).to(x.dtype)
+        dw[:, j] = (dout.to(acc) * y.to(acc)).sum(-1)
+        gu = gu32.to(x.dtype).to(acc)
+        g, u = gu[:, :I], gu[:, I:]
+        dy = (w[:, j:j + 1].to(acc) * dout.to(acc)).to(x.dtype)
+        dh = torch.einsum("th,thi->ti", dy.to(acc), w2e)
+        s = torch.sigmoid(g)
+        dgu = torch.cat([dh * u * s * (1 + g * (1 - s)), dh * g * s], 1).to(x.dtype)
+        dx = dx + torch.einsum("tn,tnh->th", dgu.to(acc), w13e).to(x.dtype).to(acc)
+    return dx.to(x.dtype), dw.to(w.dtype)
+
+
+class _ExpertsFn(torch.autograd.Function):
+    """x → ys through the two grouped launches, frozen experts.  Saves gu [P, 2I] (bf16) and the dispatch; the
+    backward is the two NN grouped launches (dh + dSwiGLU, dx rows) and the combine that sums a token's k rows."""
+
+    @staticmethod
+    def forward(ctx, x, w13, w2, pos_of, perm, offsets, k, row_class):
+        x = x.contiguous()
+        gu = torch.empty(perm.numel(), w13.shape[1], dtype=x.dtype, device=x.device)
+        hs = native().moe_gemm_swiglu(x, perm, offsets, w13, k, row_class, gu)
+        ctx.save_for_backward(gu, w13, w2, pos_of, offsets)
+        ctx.k = k
+        return native().moe_gemm_down(hs, offsets, w2, row_class)
+
+    @staticmethod
+    def backward(ctx, dys):
+        gu, w13, w2, pos_of, offsets = ctx.saved_tensors
+        dgu = native().moe_gemm_dswiglu(dys.contiguous(), gu, offsets, w2)
+        dxs = native().moe_gemm_dx(dgu, offsets, w13)
+        return native().moe_combine(dxs, pos_of, ctx.k, None, None), None, None, None, None, None, None, None
+
+
 def moe_experts(x, w13, w2, idx, w, base=None, row_class: int = 0):
     """Routed SwiGLU experts: ``base + Σ_j w[t, j] · expert_{idx[t, j]}(x[t])`` (see ``moe_experts_reference``).
 
     On HIP tensors: dispatch, two grouped GEMM launches and the combine, with no host read of the routing.
     ``row_class`` (1 skinny / 2 tiled) overrides the class the kernels pick from (T·k, E); tests only.
-    CPU tensors, ``LIPA_REFERENCE=1``, unsupported shapes and inputs that require grad run the reference."""
-    grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w13, w2, w, base))
-    if not use_native(x) or grad or not moe_gemm_supported(x, w13, w2) or idx.numel() == 0:
+    With frozen experts (``w13`` and ``w2`` do not require grad) the same launches run under autograd, bit-identical
+    in the forward, and the gradients of ``x``, ``w`` and ``base`` come from the grouped backward kernels
+    (``moe_experts_backward_reference`` is their specification).  CPU tensors, ``LIPA_REFERENCE=1``, unsupported
+    shapes and expert weights that require grad run the reference."""
+    grad = torch.is_grad_enabled()
+    if (not use_native(x) or not moe_gemm_supported(x, w13, w2) or idx.numel() == 0
+            or (grad and (w13.requires_grad or w2.requires_grad))):
         return moe_experts_reference(x, w13, w2, idx, w, base)
     d = moe_dispatch(idx, w13.shape[0])
-    hs = moe_gemm_swiglu(x, d, w13, row_class)
-    ys = moe_gemm_down(hs, d, w2, row_class)
+    if grad and x.requires_grad:
+        w13, w2 = w13.contiguous(), w2.contiguous()
+        ys = fn_apply(_ExpertsFn, x, w13, w2, d.pos_of, d.perm, d.offsets, d.k, row_class)
+    else:           # nothing flows back through the GEMMs (w and base get theirs from the combine): no gu
+        ys = moe_gemm_down(moe_gemm_swiglu(x, d, w13, row_class), d, w2, row_class)
     return moe_combine(ys, d, w, base)
 
 

@@ -3,6 +3,7 @@ GEMM launches of moe_gemm.hip, combine) against the per-expert loop it replaces 
 the segment offsets, two torch GEMMs and a SwiGLU per live expert, combine), one process, interleaved round by round.
 
     python scripts/bench_moe_gemm.py [--out profiles/r13/moe_gemm.txt]
+    python scripts/bench_moe_gemm.py --backward [--out profiles/r15/moe_gemm_bwd.txt]   # training: see main_backward
 
 Per T: device-event time of >= ITERS back-to-back calls (>= 50 ms) per round, ROUNDS rounds alternating the two;
 reported: the median of the round medians with min .. max.  Routing is uniform random; every call takes the next of
@@ -95,16 +96,75 @@ def main_fp8(a):
     return lines
 
 
+def main_backward(a):
+    """``--backward``: forward + backward of ``moe_experts`` with ``x`` requiring grad and frozen experts (the grouped
+    launches and their two backward launches) against autograd through ``moe_experts_reference``, the loop that call ran
+    before, interleaved round by round; a ratio above 1 (grouped slower) is marked with ``**``.  Then the two backward
+    kernels alone at T = 2048 (device-event time of back-to-back launches over the 16 routings' offsets)."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    w13 = (torch.randn(E, 2 * I, H, device=dev, generator=g) * H ** -0.5).bfloat16()
+    w2 = (torch.randn(E, H, I, device=dev, generator=g) * I ** -0.5).bfloat16()
+    lines = [f"routed expert MLP forward + backward (dx; frozen experts), E {E} top-{K} H {H} I {I}, bf16; {ROUNDS} rounds x "
+             f">= {ITERS} calls (>= 50 ms), reference autograd loop / grouped interleaved, {NROUTE} uniform routings in turn",
+             f"{'T':>5} | {'reference loop us (min..max)':>36} | {'grouped us (min..max)':>32} | {'grouped/loop':>12}"]
+    for T in a.tokens:
+        x = torch.randn(T, H, device=dev, generator=g).bfloat16().requires_grad_()
+        dout = torch.randn(T, H, device=dev, generator=g).bfloat16()
+        routes = []
+        for _ in range(NROUTE):
+            idx = torch.rand(T, E, device=dev, generator=g).topk(K, -1).indices
+            routes.append((idx, torch.rand(T, K, device=dev, generator=g)))
+
+        def step(fn, i):
+            return torch.autograd.grad(fn(x, w13, w2, *routes[i % NROUTE]), x, dout)[0]
+
+        fns = {"loop": lambda i: step(moe.moe_experts_reference, i), "grouped": lambda i: step(moe.moe_experts, i)}
+        diff = (fns["loop"](0).float() - fns["grouped"](0).float()).abs().max().item()
+        for fn in fns.values():
+            for i in range(NROUTE):
+                fn(i)
+        torch.cuda.synchronize()
+        iters = max(ITERS, min(1000, int(5e4 / timed(fns["grouped"], ITERS))))
+        t = {"loop": [], "grouped": []}
+        for _ in range(ROUNDS):
+            for name, fn in fns.items():
+                t[name].append(timed(fn, iters if name == "grouped" else ITERS))
+        med = {n: statistics.median(v) for n, v in t.items()}
+        cell = {n: f"{med[n]:9.1f} ({min(t[n]):.1f}..{max(t[n]):.1f})" for n in t}
+        ratio = med["grouped"] / med["loop"]
+        lines.append(f"{T:>5} | {cell['loop']:>36} | {cell['grouped']:>32} | "
+                     f"{('**%.3f**' if ratio > 1 else '%.3f') % ratio:>12}   (max |dx loop - dx grouped| {diff:.2e})")
+        print(lines[-1], flush=True)
+    T, P = 2048, 2048 * K
+    ds = [moe.moe_dispatch(torch.rand(T, E, device=dev, generator=g).topk(K, -1).indices, E) for _ in range(NROUTE)]
+    dys = torch.randn(P, H, device=dev, generator=g).bfloat16()
+    gu = torch.randn(P, 2 * I, device=dev, generator=g).bfloat16()
+    dgu = native().moe_gemm_dswiglu(dys, gu, ds[0].offsets, w2)
+    kern = {"moe_gemm_nn_k<dswiglu>": (lambda i: native().moe_gemm_dswiglu(dys, gu, ds[i % NROUTE].offsets, w2), 2 * P * H * I),
+            "moe_gemm_nn_k<dx>": (lambda i: native().moe_gemm_dx(dgu, ds[i % NROUTE].offsets, w13), 4 * P * H * I)}
+    lines.append(f"backward kernels alone, T {T} (P {P}), {ROUNDS} rounds x 200 launches, median (min..max)")
+    for name, (fn, flop) in kern.items():
+        timed(fn, NROUTE)
+        v = [timed(fn, 200) for _ in range(ROUNDS)]
+        med = statistics.median(v)
+        lines.append(f"{name:>24} | {med:8.1f} us ({min(v):.1f}..{max(v):.1f}) | {flop / med / 1e9:.3f} PFLOP/s")
+        print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--tokens", type=int, nargs="+", default=[1, 8, 64, 256, 2048])
+    ap.add_argument("--tokens", type=int, nargs="+", default=None)
     ap.add_argument("--fp8", action="store_true", help="bf16 experts against FP8 (e4m3) experts instead of loop / grouped")
+    ap.add_argument("--backward", action="store_true", help="forward + backward under autograd, reference loop / grouped")
     a = ap.parse_args()
+    a.tokens = a.tokens or ([512, 2048, 8192] if a.backward else [1, 8, 64, 256, 2048])
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe_gemm: needs the GPU (no CPU fall-back for a timing)")
-    if a.fp8:
-        text = "\n".join(main_fp8(a)) + "\n"
+    if a.fp8 or a.backward:
+        text = "\n".join(main_backward(a) if a.backward else main_fp8(a)) + "\n"
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:

@@ -172,7 +172,27 @@ def cmd_lm_train(a, strategy="single"):
 
 
 # ============================================================================ track E
-def _load_base(a, preset, device):
+def _finetune_moe_expert_dtype(a, preset) -> bool:
+    """``finetune --moe-expert-dtype``: whether the frozen experts are held as e4m3 codes.  What that does not serve is
+    refused here, before anything loads, each message naming the flag."""
+    from ..models.common import normalize_moe_expert_dtype
+    try:
+        if normalize_moe_expert_dtype(getattr(a, "moe_expert_dtype", None)) != "fp8":
+            return False
+    except ValueError as e:
+        raise SystemExit(str(e))
+    path = a.model_path if a.model_path and not a.random_init else "random:" + (a.random_init or preset.model)
+    if not _is_moe(path):
+        raise SystemExit("--moe-expert-dtype fp8 needs a Qwen3-MoE model: this model has no experts")
+    if preset.quant:
+        raise SystemExit(f"--moe-expert-dtype fp8 cannot be combined with the preset's {preset.quant} base "
+                         f"(--preset {a.preset}): choose a preset without quantisation")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--moe-expert-dtype fp8 fine-tunes on one GPU: WORLD_SIZE > 1 is not supported")
+    return True
+
+
+def _load_base(a, preset, device, moe_fp8=False):
     from ..models.qwen3 import BitsAndBytesConfig, Qwen3ForCausalLM, qwen3_config
     qc = BitsAndBytesConfig(load_in_4bit=True, bnb_4bit_quant_type="nf4", bnb_4bit_use_double_quant=True,
                             bnb_4bit_compute_dtype=torch.bfloat16) if preset.quant == "nf4" else None
@@ -182,9 +202,12 @@ def _load_base(a, preset, device):
         if qc is not None:
             from ..peft.lora import quantize_model_nf4
             quantize_model_nf4(m)
+        if moe_fp8:                     # after initialisation, layer by layer
+            m.quantize_experts_fp8()
         return m
     return Qwen3ForCausalLM.from_pretrained(a.model_path, dtype=torch.bfloat16, device=device, quantization_config=qc,
-                                            rope_scaling=None if preset.rope_scaling == "none" else "keep")
+                                            rope_scaling=None if preset.rope_scaling == "none" else "keep",
+                                            moe_expert_dtype="fp8" if moe_fp8 else None)
 
 
 def cmd_finetune(a):
@@ -195,12 +218,13 @@ def cmd_finetune(a):
                               SFTDataset, SyntheticLMDataset, load_records, load_tokenizer, synthetic_self_cognition)
     from ..train.trainer import Trainer, TrainingArguments
     p = PRESETS[a.preset]
+    moe_fp8 = _finetune_moe_expert_dtype(a, p)   # refusals before a process group or a model exists
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         D.init_distributed(timeout_s=1800)
     dev = _device()
     if dev.type == "cuda":
         torch.cuda.set_device(dev)
-    model = _load_base(a, p, dev)
+    model = _load_base(a, p, dev, moe_fp8)
     if p.quant:
         model = prepare_model_for_kbit_training(model, use_gradient_checkpointing=p.grad_ckpt and not a.no_grad_ckpt)
     elif p.grad_ckpt and not a.no_grad_ckpt:
@@ -1083,6 +1107,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resume", default=None)
     p.add_argument("--metrics-jsonl", dest="metrics_jsonl")
     p.add_argument("--synthetic-samples", dest="synthetic_samples", type=int, default=108)
+    p.add_argument("--moe-expert-dtype", "--moe_expert_dtype", dest="moe_expert_dtype", default="auto",
+                   help="Qwen3-MoE expert weights: auto | bfloat16 (as the checkpoint holds them) or fp8 | fp8_e4m3 "
+                        "(weight-only e4m3 codes, one scale per expert row, bf16 activations: half the expert bytes; "
+                        "one GPU)")
     p.set_defaults(fn=cmd_finetune)
 
     for name, fn in (("chat", cmd_chat), ("infer", cmd_infer)):

@@ -104,7 +104,9 @@ int moe_gemm_class(int, int);
 void launch_moe_gemm(int, int, const void*, const int*, int, const int*, const void*, void*, void*, int, int, int, int,
                      hipStream_t);
 void launch_moe_gemm_bwd(int, const void*, const int*, const void*, const void*, void*, int, int, int, int, hipStream_t);
-void launch_moe_gemm_fp8(int, int, const void*, const int*, int, const int*, const void*, const float*, void*, int, int,
+void launch_moe_gemm_fp8_bwd(int, const void*, const int*, const void*, const float*, const float*, const void*, void*, int,
+                             int, int, int, hipStream_t);
+void launch_moe_gemm_fp8(int, int, const void*, const int*, int, const int*, const void*, const float*, void*, void*, int, int,
                          int, int, hipStream_t);
 int lora_acc_chunks(int M, int K);
 void launch_lora_proj2(const void*, int, const void*, const void*, int, int, int, float*, int, void*, int, int, uint64_t, float, float,
@@ -2285,27 +2287,34 @@ Tensor moe_gemm_dx(Tensor dgu, Tensor offsets, Tensor w13) {
 
 // ---- the same two stages over e4m3 expert weights: codes [E, NW, K] + fp32 scale [E, NW] (W8A16, moe_gemm.hip)
 namespace {
-void moe_gemm_fp8_check(const char* who, const Tensor& a, const Tensor& offsets, const Tensor& c, const Tensor& s,
-                        int64_t H, int64_t I) {
-  TORCH_CHECK(a.is_cuda() && c.is_cuda() && s.is_cuda() && offsets.is_cuda(), who, ": device tensors");
+// codes [E, rows, K] under bf16 activations; the scale-free half of the checks (moe_gemm_dx_fp8 reads no scale)
+void moe_gemm_codes_check(const char* who, const Tensor& a, const Tensor& offsets, const Tensor& c, int64_t H, int64_t I) {
+  TORCH_CHECK(a.is_cuda() && c.is_cuda() && offsets.is_cuda(), who, ": device tensors");
   TORCH_CHECK(a.scalar_type() == at::kBFloat16, who, ": bf16 activations");
   TORCH_CHECK(c.scalar_type() == at::kFloat8_e4m3fn || c.scalar_type() == at::kByte, who, ": codes must be e4m3");
-  TORCH_CHECK(c.is_contiguous() && s.is_contiguous(), who, ": codes and scales must be contiguous");
+  TORCH_CHECK(c.is_contiguous(), who, ": codes and scales must be contiguous");
   TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.dim() == 1 && offsets.is_contiguous(), who,
               ": offsets int32 [E+1]");
   TORCH_CHECK(c.dim() == 3 && c.size(0) == offsets.numel() - 1 && c.size(0) >= 1 && c.size(0) <= 128, who,
               ": 1 <= E <= 128 experts, offsets [E+1]");
+  TORCH_CHECK(H % 64 == 0 && I % 64 == 0 && H > 0 && I > 0, who, ": H % 64 == 0 and I % 64 == 0");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              who, ": 16-byte aligned operands");
+}
+void moe_gemm_fp8_check(const char* who, const Tensor& a, const Tensor& offsets, const Tensor& c, const Tensor& s,
+                        int64_t H, int64_t I) {
+  TORCH_CHECK(s.is_cuda(), who, ": device tensors");
+  moe_gemm_codes_check(who, a, offsets, c, H, I);
+  TORCH_CHECK(s.is_contiguous(), who, ": codes and scales must be contiguous");
   TORCH_CHECK(s.scalar_type() == at::kFloat && s.dim() == 2 && s.size(0) == c.size(0) && s.size(1) == c.size(1), who,
               ": scales fp32 [E, rows], one per code row");
-  TORCH_CHECK(H % 64 == 0 && I % 64 == 0 && H > 0 && I > 0, who, ": H % 64 == 0 and I % 64 == 0");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(s.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
-              who, ": 16-byte aligned operands");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(s.data_ptr()) % 16 == 0, who, ": 16-byte aligned operands");
 }
 }  // namespace
 
+// gu (optional, written): bf16 [T*k, 2I], the scaled g and u of every row rounded once, saved for moe_gemm_dswiglu_fp8
 Tensor moe_gemm_swiglu_fp8(Tensor x, Tensor perm, Tensor offsets, Tensor c13, Tensor s13, int64_t k,
-                           int64_t row_class) {
+                           int64_t row_class, optional<Tensor> gu) {
   CHECK_CONTIG(x); CHECK_CONTIG(perm);
   TORCH_CHECK(x.dim() == 2 && c13.dim() == 3 && c13.size(2) == x.size(1) && c13.size(1) % 2 == 0,
               "moe_gemm_swiglu_fp8: x [T, H], c13 [E, 2I, H]");
@@ -2314,10 +2323,13 @@ Tensor moe_gemm_swiglu_fp8(Tensor x, Tensor perm, Tensor offsets, Tensor c13, Te
   TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == at::kInt && k >= 1 && perm.numel() == x.size(0) * k &&
               perm.numel() < (1 << 24), "moe_gemm_swiglu_fp8: perm int32 [T*k]");
   const int P = perm.numel(), E = c13.size(0);
+  if (gu.has_value())
+    TORCH_CHECK(gu->is_cuda() && gu->is_contiguous() && gu->scalar_type() == at::kBFloat16 && gu->dim() == 2 &&
+                gu->size(0) == P && gu->size(1) == 2 * I, "moe_gemm_swiglu_fp8: gu bf16 [T*k, 2I]");
   Tensor hs = torch::empty({P, I}, x.options());
   if (P) launch_moe_gemm_fp8(0, moe_gemm_pick(row_class, P, E), x.data_ptr(), perm.data_ptr<int>(), (int)k,
-                             offsets.data_ptr<int>(), c13.data_ptr(), s13.data_ptr<float>(), hs.data_ptr(), P, E,
-                             (int)I, (int)H, stream());
+                             offsets.data_ptr<int>(), c13.data_ptr(), s13.data_ptr<float>(), hs.data_ptr(),
+                             gu.has_value() ? gu->data_ptr() : nullptr, P, E, (int)I, (int)H, stream());
   return hs;
 }
 
@@ -2330,8 +2342,47 @@ Tensor moe_gemm_down_fp8(Tensor hs, Tensor offsets, Tensor c2, Tensor s2, int64_
   const int P = hs.size(0), E = c2.size(0);
   Tensor ys = torch::empty({P, H}, hs.options());
   if (P) launch_moe_gemm_fp8(1, moe_gemm_pick(row_class, P, E), hs.data_ptr(), nullptr, 1, offsets.data_ptr<int>(),
-                             c2.data_ptr(), s2.data_ptr<float>(), ys.data_ptr(), P, E, (int)H, (int)I, stream());
+                             c2.data_ptr(), s2.data_ptr<float>(), ys.data_ptr(), nullptr, P, E, (int)H, (int)I,
+                             stream());
   return ys;
+}
+
+// ---- input gradients over the codes, frozen experts (moe_gemm_nn_fp8_k): c2 and c13 are read as they are
+// dgu' [P, 2I] = dSwiGLU(dys · wq2[e]; gu) · s13[e], wq2 = bf16(val(c2)·s2): dys [P, H], gu [P, 2I] from
+// moe_gemm_swiglu_fp8, c2 [E, H, I] + s2 [E, H], s13 [E, 2I] (the scale of the second GEMM's reduction index, folded)
+Tensor moe_gemm_dswiglu_fp8(Tensor dys, Tensor gu, Tensor offsets, Tensor c2, Tensor s2, Tensor s13) {
+  CHECK_CONTIG(dys); CHECK_CONTIG(gu);
+  TORCH_CHECK(dys.dim() == 2 && gu.dim() == 2 && c2.dim() == 3 && c2.size(1) == dys.size(1) &&
+              gu.size(0) == dys.size(0) && gu.size(1) == 2 * c2.size(2),
+              "moe_gemm_dswiglu_fp8: dys [P, H], gu [P, 2I], c2 [E, H, I]");
+  const int64_t H = c2.size(1), I = c2.size(2);
+  moe_gemm_fp8_check("moe_gemm_dswiglu_fp8", dys, offsets, c2, s2, H, I);
+  TORCH_CHECK(gu.is_cuda() && gu.scalar_type() == at::kBFloat16 && reinterpret_cast<uintptr_t>(gu.data_ptr()) % 16 == 0,
+              "moe_gemm_dswiglu_fp8: gu bf16 on the device, 16-byte aligned");
+  TORCH_CHECK(s13.is_cuda() && s13.is_contiguous() && s13.scalar_type() == at::kFloat && s13.dim() == 2 &&
+              s13.size(0) == c2.size(0) && s13.size(1) == 2 * I && reinterpret_cast<uintptr_t>(s13.data_ptr()) % 16 == 0,
+              "moe_gemm_dswiglu_fp8: s13 fp32 [E, 2I], contiguous and 16-byte aligned");
+  TORCH_CHECK(dys.size(0) < (1 << 24), "moe_gemm_dswiglu_fp8: < 2^24 rows");
+  const int P = dys.size(0), E = c2.size(0);
+  Tensor dgu = torch::empty({P, 2 * I}, dys.options());
+  if (P) launch_moe_gemm_fp8_bwd(0, dys.data_ptr(), offsets.data_ptr<int>(), c2.data_ptr(), s2.data_ptr<float>(),
+                                 s13.data_ptr<float>(), gu.data_ptr(), dgu.data_ptr(), P, E, (int)I, (int)H, stream());
+  return dgu;
+}
+
+// dxs [P, H] = dgu' · val(c13[e]): dgu' [P, 2I] with s13 already folded in, c13 [E, 2I, H]; no scale is read
+Tensor moe_gemm_dx_fp8(Tensor dgu, Tensor offsets, Tensor c13) {
+  CHECK_CONTIG(dgu);
+  TORCH_CHECK(dgu.dim() == 2 && c13.dim() == 3 && c13.size(1) == dgu.size(1) && c13.size(1) % 2 == 0,
+              "moe_gemm_dx_fp8: dgu [P, 2I], c13 [E, 2I, H]");
+  const int64_t H = c13.size(2), I = c13.size(1) / 2;
+  moe_gemm_codes_check("moe_gemm_dx_fp8", dgu, offsets, c13, H, I);
+  TORCH_CHECK(dgu.size(0) < (1 << 24), "moe_gemm_dx_fp8: < 2^24 rows");
+  const int P = dgu.size(0), E = c13.size(0);
+  Tensor dxs = torch::empty({P, H}, dgu.options());
+  if (P) launch_moe_gemm_fp8_bwd(1, dgu.data_ptr(), offsets.data_ptr<int>(), c13.data_ptr(), nullptr, nullptr, nullptr,
+                                 dxs.data_ptr(), P, E, (int)H, (int)(2 * I), stream());
+  return dxs;
 }
 
 int64_t moe_gemm_class_py(int64_t P, int64_t E) { return moe_gemm_class((int)P, (int)E); }
@@ -2398,7 +2449,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gemm_dx", &moe_gemm_dx, py::arg("dgu"), py::arg("offsets"), py::arg("w13"));
   m.def("moe_gemm_down", &moe_gemm_down, py::arg("hs"), py::arg("offsets"), py::arg("w2"), py::arg("row_class") = 0);
   m.def("moe_gemm_swiglu_fp8", &moe_gemm_swiglu_fp8, py::arg("x"), py::arg("perm"), py::arg("offsets"),
-        py::arg("c13"), py::arg("s13"), py::arg("k"), py::arg("row_class") = 0);
+        py::arg("c13"), py::arg("s13"), py::arg("k"), py::arg("row_class") = 0, py::arg("gu") = py::none());
+  m.def("moe_gemm_dswiglu_fp8", &moe_gemm_dswiglu_fp8, py::arg("dys"), py::arg("gu"), py::arg("offsets"), py::arg("c2"),
+        py::arg("s2"), py::arg("s13"));
+  m.def("moe_gemm_dx_fp8", &moe_gemm_dx_fp8, py::arg("dgu"), py::arg("offsets"), py::arg("c13"));
   m.def("moe_gemm_down_fp8", &moe_gemm_down_fp8, py::arg("hs"), py::arg("offsets"), py::arg("c2"), py::arg("s2"),
         py::arg("row_class") = 0);
   m.def("moe_gemm_class", &moe_gemm_class_py);

@@ -72,6 +72,26 @@
 // values kq | 4·(g & 1) on them, so the 8 rows land in 8 distinct 32-B bank slots and cover the 64 banks once.  The
 // DMA's own writes are 1 KiB contiguous whatever the source.  K is never ragged (H % 64 == 2I % 64 == 0); ragged N
 // (I or H not a multiple of 128) is clamped per 16-B chunk on load and masked on store.
+//
+// Backward over FP8 codes (moe_gemm_nn_fp8_k; frozen e4m3 experts under adapters).  The forward FP8 kernels take the
+// same GU parameter (gu = the scaled fp32 accumulators rounded once; hs still from the unrounded values).  The NN
+// kernel above is kept whole (tiles, grid, find_tile, A rows by LDS-DMA, transposed fragment reads with woff, the
+// image and its swizzle, ascending K, row invariance) except for the W stage, which is the codes c2 [E, H, I] and
+// c13 [E, 2I, H] as they are: 64 k-rows × 128 codes = 8 KiB, global → registers one stage ahead as in
+// moe_gemm_tiled_fp8_k, converted once per workgroup.  Thread tid loads 16 codes of k-row tid / 8 (and + 32) at source
+// column min(n0 + 16·m, N − 16), m = tid % 8 (N % 64 == 0: a pair is wholly in or out of the matrix).  16 codes are one
+// 32-B column pair of the image, so they become two bf16x8 and two ds_write_b128 at pair m ^ nn_swz(k) of the k-row;
+// nn_swz(k + 32) == nn_swz(k), so the second load lands 32 rows further at the same offset.  The writes and the banks:
+// a wave holds k-rows 8w .. 8w + 7 (8 lanes each), 256 B per k-row, i.e. one contiguous 2-KiB run of the image; m ↦
+// m ^ nn_swz(k) permutes the 8 pairs of a k-row, so the wave's two ds_write_b128 (lower and upper 16 B of every pair)
+// together write each of the run's 128 16-B slots exactly once.  The reads are those of the bf16 kernel and the bank
+// argument above holds for them unchanged, since the image is the same.
+// Where the scales go: both run along the reduction index of their GEMM and cannot meet the accumulator.
+//   dswiglu (W = c2, K = H): the conversion multiplies by s2[e, k-row] in fp32 before the bf16 rounding, one scalar per
+//            load fetched with the codes: the image holds wq2 = bf16(fp32(val(c2))·s2), the one place where a weight is
+//            rounded a second time.  The epilogue multiplies dg by s13[e, n] and du by s13[e, I + n] in fp32 before
+//            their single rounding (two more 16-B loads per lane and fragment), which folds the second GEMM's scale.
+//   dx      (W = c13, K = 2I): plain cvt16 over the exact code values, no scale anywhere.
 #include "common.h"
 
 using namespace lipa;
@@ -468,11 +488,11 @@ __device__ __forceinline__ f32x4 scaled(const f32x4& a, const f32x4& s) {
 // As skinny_rows, with wr0 / wr1 pointing at code bytes.  Lane (li, g) loads bytes 64s + 16g .. + 15 of weight row
 // li: codes 0..7 are its A operand of k-step 2s, codes 8..15 of k-step 2s + 1, and the x rows are read at the
 // same k (64s + 16g + 8h + i), so both operands of an MFMA step hold the same 32 k-values in the same slots.
-template <bool SWIGLU, int MT>
+template <bool SWIGLU, bool GU, int MT>
 __device__ __forceinline__ void skinny8_rows(const bf16* __restrict__ A, const int* __restrict__ perm, int kdiv,
                                              const uint8_t* wr0, const uint8_t* wr1, const f32x4& sc0,
-                                             const f32x4& sc1, bf16* __restrict__ out, int ldo, int K, int r0, int r1,
-                                             int col0, int col1) {
+                                             const f32x4& sc1, bf16* __restrict__ out, bf16* __restrict__ gu, int ldo,
+                                             int K, int r0, int r1, int col0, int col1) {
   const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
   const bf16* xr[MT];
 #pragma unroll
@@ -514,17 +534,19 @@ __device__ __forceinline__ void skinny8_rows(const bf16* __restrict__ A, const i
   for (int mt = 0; mt < MT; ++mt) {
     const int p = r0 + 16 * mt + li;
     if (p < r1)
-      store_pair<SWIGLU>(out, ldo, p, col0 + 4 * g, col1 + 4 * g, scaled(acc[0][mt], sc0), scaled(acc[1][mt], sc1));
+      store_pair<SWIGLU, GU>(out, ldo, p, col0 + 4 * g, col1 + 4 * g, scaled(acc[0][mt], sc0), scaled(acc[1][mt], sc1),
+                             gu);
   }
 }
 
-// W [E, NW, K] e4m3 codes, scale fp32 [E, NW]; everything else as moe_gemm_skinny_k.  K % 64 == 0, N % 64 == 0.
-template <bool SWIGLU>
+// W [E, NW, K] e4m3 codes, scale fp32 [E, NW]; everything else as moe_gemm_skinny_k (GU: the scaled g and u, rounded
+// once, go to gu [P, 2N]).  K % 64 == 0, N % 64 == 0.
+template <bool SWIGLU, bool GU = false>
 __global__ __launch_bounds__(256) void moe_gemm_skinny_fp8_k(const bf16* __restrict__ A, const int* __restrict__ perm,
                                                              int kdiv, const int* __restrict__ offsets,
                                                              const uint8_t* __restrict__ W,
                                                              const float* __restrict__ scale, bf16* __restrict__ out,
-                                                             int N, int K, int nblk) {
+                                                             bf16* __restrict__ gu, int N, int K, int nblk) {
   const int e = blockIdx.x / nblk, bn = blockIdx.x % nblk;
   const int s0 = offsets[e], s1 = offsets[e + 1];
   if (s1 <= s0) return;
@@ -541,9 +563,9 @@ __global__ __launch_bounds__(256) void moe_gemm_skinny_fp8_k(const bf16* __restr
   const f32x4 sc1 = *reinterpret_cast<const f32x4*>(se + n1 + 4 * g);
   for (int r0 = s0; r0 < s1; r0 += 64) {
     const int r1 = min(s1, r0 + 64), n = r1 - r0;
-    if (n <= 16) skinny8_rows<SWIGLU, 1>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, N, K, r0, r1, col0, col1);
-    else if (n <= 32) skinny8_rows<SWIGLU, 2>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, N, K, r0, r1, col0, col1);
-    else skinny8_rows<SWIGLU, 4>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, N, K, r0, r1, col0, col1);
+    if (n <= 16) skinny8_rows<SWIGLU, GU, 1>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, gu, N, K, r0, r1, col0, col1);
+    else if (n <= 32) skinny8_rows<SWIGLU, GU, 2>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, gu, N, K, r0, r1, col0, col1);
+    else skinny8_rows<SWIGLU, GU, 4>(A, perm, kdiv, wr0, wr1, sc0, sc1, out, gu, N, K, r0, r1, col0, col1);
   }
 }
 
@@ -552,12 +574,12 @@ __global__ __launch_bounds__(256) void moe_gemm_skinny_fp8_k(const bf16* __restr
 // into registers (two 16-byte loads per thread: row tid/4 (+64), quarter tid%4) while stage kt's MFMAs run, are
 // converted once, and are written as the two bf16 chunks 2q, 2q + 1 of the swizzled image the DMA would have
 // written.  The gathered x rows keep going by LDS-DMA.  One barrier per stage, as before.
-template <bool SWIGLU>
+template <bool SWIGLU, bool GU = false>
 __global__ __launch_bounds__(256) void moe_gemm_tiled_fp8_k(const bf16* __restrict__ A, const int* __restrict__ perm,
                                                             int kdiv, const int* __restrict__ offsets,
                                                             const uint8_t* __restrict__ W,
                                                             const float* __restrict__ scale, bf16* __restrict__ out,
-                                                            int E, int N, int K, int nblk) {
+                                                            bf16* __restrict__ gu, int E, int N, int K, int nblk) {
   __shared__ __attribute__((aligned(16))) bf16 sx[2][MG_BM * MG_BK];
   __shared__ __attribute__((aligned(16))) bf16 sw[2][MG_BN * MG_BK];
   int e, r0, s1;
@@ -664,7 +686,165 @@ __global__ __launch_bounds__(256) void moe_gemm_tiled_fp8_k(const bf16* __restri
     for (int mi = 0; mi < 2; ++mi) {
       const int p = r0 + wm * 32 + mi * 16 + li;
       if (p >= s1) continue;
-      store_pair<SWIGLU>(out, N, p, col0, col0 + 16, scaled(acc[2 * c][mi], sc0), scaled(acc[2 * c + 1][mi], sc1));
+      store_pair<SWIGLU, GU>(out, N, p, col0, col0 + 16, scaled(acc[2 * c][mi], sc0), scaled(acc[2 * c + 1][mi], sc1),
+                             gu);
+    }
+  }
+}
+
+// ------------------------------------------------------------------ backward over codes: NN grouped GEMM
+// 16 e4m3 codes times one fp32 scale → 2 × 8 bf16: bf16(fp32(val)·s), one fp32 multiply and one rounding to nearest even
+__device__ __forceinline__ void cvt16_scaled(const u32x4& c, float s, bf16x8& a, bf16x8& b) {
+  float f[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], true);
+    f[4 * i] = lo[0] * s; f[4 * i + 1] = lo[1] * s; f[4 * i + 2] = hi[0] * s; f[4 * i + 3] = hi[1] * s;
+  }
+  a = bf16x8{(bf16)f[0], (bf16)f[1], (bf16)f[2], (bf16)f[3], (bf16)f[4], (bf16)f[5], (bf16)f[6], (bf16)f[7]};
+  b = bf16x8{(bf16)f[8], (bf16)f[9], (bf16)f[10], (bf16)f[11], (bf16)f[12], (bf16)f[13], (bf16)f[14], (bf16)f[15]};
+}
+
+// moe_gemm_nn_k over e4m3 codes W [E, K, N] (n contiguous), read as they are; A, tiles, grid, fragment reads, MFMA loop
+// and row invariance as there.  The W stage of kt + 1 (64 k-rows × 128 codes) is loaded into registers while stage kt's
+// MFMAs run (two 16-byte loads per thread: k-row tid / 8 (+ 32), column pair tid % 8), converted once and written as
+// pair m ^ nn_swz(k) of the swizzled bf16 image the DMA of the bf16 kernel would have written.
+//   DSWIGLU (A = dys, W = c2, K = H, N = I): kscale = s2 [E, K] multiplies the code values of its k-row before the bf16
+//     rounding (the image is wq2); nscale = s13 [E, 2N] multiplies dg (columns n) and du (columns N + n) in fp32 before
+//     their one rounding.  out [P, 2N].
+//   else (A = dgu', W = c13, K = 2I, N = H): the exact code values, no scale.  out [P, N].
+// K % 64 == 0, N % 64 == 0.
+template <bool DSWIGLU>
+__global__ __launch_bounds__(256) void moe_gemm_nn_fp8_k(const bf16* __restrict__ A, const int* __restrict__ offsets,
+                                                         const uint8_t* __restrict__ W,
+                                                         const float* __restrict__ kscale,
+                                                         const float* __restrict__ nscale, const bf16* __restrict__ gu,
+                                                         bf16* __restrict__ out, int E, int N, int K, int nblk) {
+  __shared__ __attribute__((aligned(16))) bf16 sx[2][MG_BM * MG_BK];
+  __shared__ __attribute__((aligned(16))) bf16 sw[2][MG_BK * MG_BN];
+  int e, r0, s1;
+  if (!find_tile(offsets, E, blockIdx.x / nblk, e, r0, s1)) return;
+  const int n0 = (blockIdx.x % nblk) * MG_BN;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
+  const int wm = w >> 1, wn = w & 1;          // 2 × 2 waves: 32 rows × 64 output columns each
+
+  const bf16* xsrc[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = (q * 4 + w) * 8 + (lane >> 3);
+    const int p = min(r0 + r, s1 - 1);
+    xsrc[q] = A + (size_t)p * K + 8 * ((lane & 7) ^ (r & 7));
+  }
+  // W: k-rows kr and kr + 32 of a stage, 16 codes of column pair m, clamped into the row when N is ragged (those
+  // columns are masked on store); both land at pair m ^ nn_swz(kr) of their k-row
+  const int kr = tid >> 3, m = tid & 7;
+  const uint8_t* wsrc = W + ((size_t)e * K + kr) * N + min(n0 + 16 * m, N - 16);
+  const float* ksrc = DSWIGLU ? kscale + (size_t)e * K + kr : nullptr;
+  const int wdst = kr * MG_BN + 16 * (m ^ nn_swz(kr));
+  u32x4 wreg[2];
+  float ksc[2];
+  auto issue_x = [&](int buf, int k0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) dma16(xsrc[q] + k0, &sx[buf][(q * 4 + w) * 8 * MG_BK]);
+  };
+  auto load_w = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      wreg[q] = *reinterpret_cast<const u32x4*>(wsrc + (size_t)(k0 + 32 * q) * N);
+      if (DSWIGLU) ksc[q] = ksrc[k0 + 32 * q];
+    }
+  };
+  auto put_w = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      bf16x8 lo, hi;
+      if (DSWIGLU) cvt16_scaled(wreg[q], ksc[q], lo, hi);
+      else cvt16(wreg[q], lo, hi);
+      bf16* dst = &sw[buf][q * 32 * MG_BN + wdst];
+      *reinterpret_cast<bf16x8*>(dst) = lo;
+      *reinterpret_cast<bf16x8*>(dst + 8) = hi;
+    }
+  };
+
+  const int kq = (lane >> 2) & 3, kp = lane & 3;
+  int woff[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) woff[j] = (8 * g + kq) * MG_BN + 16 * ((wn * 4 + j) ^ (kq | ((g & 1) << 2))) + 4 * kp;
+
+  f32x4 acc[4][2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) acc[j][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = K / MG_BK;
+  issue_x(0, 0);
+  load_w(0);
+  put_w(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this lane's part of A stage kt has landed
+    __syncthreads();                                        // stage kt visible; every wave is done reading stage kt-1
+    if (kt + 1 < nk) {
+      issue_x(buf ^ 1, (kt + 1) * MG_BK);
+      load_w((kt + 1) * MG_BK);                             // both fly under this stage's MFMAs
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int c = ks * 4 + g;
+      bf16x8 b[2], a[4];
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        const int r = wm * 32 + mi * 16 + li;
+        b[mi] = *reinterpret_cast<const bf16x8*>(&sx[buf][r * MG_BK + 8 * (c ^ (r & 7))]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bf16* pw = &sw[buf][ks * 32 * MG_BN + woff[j]];
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)pw);
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(pw + 4 * MG_BN));
+        a[j] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+          acc[j][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], b[mi], acc[j][mi], 0, 0, 0);
+    }
+    if (kt + 1 < nk) put_w(buf ^ 1);                        // nobody reads that buffer before the next barrier
+  }
+
+  // acc[j][mi][i] = C[p = r0 + 32·wm + 16·mi + li][n = n0 + 64·wn + 16·j + 4·g + i]
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = n0 + wn * 64 + 16 * j + 4 * g;
+    if (col >= N) continue;                                 // N % 4 == 0: a lane's four columns are in or out together
+    f32x4 sg, su;
+    if (DSWIGLU) {
+      const float* se = nscale + (size_t)e * 2 * N + col;
+      sg = *reinterpret_cast<const f32x4*>(se);
+      su = *reinterpret_cast<const f32x4*>(se + N);
+    }
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+      const int p = r0 + wm * 32 + mi * 16 + li;
+      if (p >= s1) continue;
+      const f32x4& dh = acc[j][mi];
+      if (DSWIGLU) {
+        const size_t at = (size_t)p * 2 * N + col;
+        const bf16x4 gv = *reinterpret_cast<const bf16x4*>(gu + at), uv = *reinterpret_cast<const bf16x4*>(gu + at + N);
+        float dg[4], du[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float gg = (float)gv[i], uu = (float)uv[i], s = 1.f / (1.f + __expf(-gg));
+          dg[i] = dh[i] * uu * s * (1.f + gg * (1.f - s)) * sg[i];
+          du[i] = dh[i] * gg * s * su[i];
+        }
+        store4(out + at, dg[0], dg[1], dg[2], dg[3]);
+        store4(out + at + N, du[0], du[1], du[2], du[3]);
+      } else {
+        store4(out + (size_t)p * N + col, dh[0], dh[1], dh[2], dh[3]);
+      }
     }
   }
 }
@@ -714,28 +894,49 @@ void launch_moe_gemm_bwd(int stage, const void* A, const int* offsets, const voi
 }
 
 // The same two stages over e4m3 codes W with one fp32 scale per (expert, weight row): scale [E, 2N] / [E, N].
-// N % 64 == 0 and K % 64 == 0 (a 16-byte code load is half a 64-deep block of one row).
+// N % 64 == 0 and K % 64 == 0 (a 16-byte code load is half a 64-deep block of one row).  gu as in launch_moe_gemm.
 void launch_moe_gemm_fp8(int stage, int cls, const void* A, const int* perm, int kdiv, const int* offsets,
-                         const void* W, const float* scale, void* out, int P, int E, int N, int K, hipStream_t st) {
+                         const void* W, const float* scale, void* out, void* gu, int P, int E, int N, int K,
+                         hipStream_t st) {
   const int nblk = stage == 0 ? (N + 63) / 64 : (N + 127) / 128;
+  const bf16* a = (const bf16*)A;
   const uint8_t* Wc = (const uint8_t*)W;
+  bf16 *o = (bf16*)out, *q = (bf16*)gu;
   if (cls == 1) {
     const int grid = E * nblk;
-    if (stage == 0)
-      moe_gemm_skinny_fp8_k<true><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, Wc, scale, (bf16*)out, N,
-                                                        K, nblk);
+    if (stage == 0 && q)
+      moe_gemm_skinny_fp8_k<true, true><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, Wc, scale, o, q, N, K, nblk);
+    else if (stage == 0)
+      moe_gemm_skinny_fp8_k<true><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, Wc, scale, o, nullptr, N, K, nblk);
     else
-      moe_gemm_skinny_fp8_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, Wc, scale, (bf16*)out,
-                                                         N, K, nblk);
+      moe_gemm_skinny_fp8_k<false><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, Wc, scale, o, nullptr, N, K, nblk);
   } else {
     const int tiles = P < P / MG_BM + E ? P : P / MG_BM + E;
     const int grid = tiles * nblk;
-    if (stage == 0)
-      moe_gemm_tiled_fp8_k<true><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, Wc, scale, (bf16*)out, E,
-                                                       N, K, nblk);
+    if (stage == 0 && q)
+      moe_gemm_tiled_fp8_k<true, true><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, Wc, scale, o, q, E, N, K, nblk);
+    else if (stage == 0)
+      moe_gemm_tiled_fp8_k<true><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, Wc, scale, o, nullptr, E, N, K, nblk);
     else
-      moe_gemm_tiled_fp8_k<false><<<grid, 256, 0, st>>>((const bf16*)A, perm, kdiv, offsets, Wc, scale, (bf16*)out, E,
-                                                        N, K, nblk);
+      moe_gemm_tiled_fp8_k<false><<<grid, 256, 0, st>>>(a, perm, kdiv, offsets, Wc, scale, o, nullptr, E, N, K, nblk);
   }
+  LIPA_CHECK_LAUNCH();
+}
+
+// Backward over the codes, frozen experts.  stage 0: A = dys [P, K=H], W = c2 [E, K, N=I], kscale = s2 [E, K],
+// nscale = s13 [E, 2N], gu [P, 2N] → out = dgu' [P, 2N] (s13 folded in); stage 1: A = dgu' [P, K=2I],
+// W = c13 [E, K, N=H], no scales → out = dxs [P, N].  One tiled class for every P; N % 64 == 0, K % 64 == 0.
+void launch_moe_gemm_fp8_bwd(int stage, const void* A, const int* offsets, const void* W, const float* kscale,
+                             const float* nscale, const void* gu, void* out, int P, int E, int N, int K,
+                             hipStream_t st) {
+  const int nblk = (N + MG_BN - 1) / MG_BN;
+  const int tiles = P < P / MG_BM + E ? P : P / MG_BM + E;
+  const int grid = tiles * nblk;
+  if (stage == 0)
+    moe_gemm_nn_fp8_k<true><<<grid, 256, 0, st>>>((const bf16*)A, offsets, (const uint8_t*)W, kscale, nscale,
+                                                  (const bf16*)gu, (bf16*)out, E, N, K, nblk);
+  else
+    moe_gemm_nn_fp8_k<false><<<grid, 256, 0, st>>>((const bf16*)A, offsets, (const uint8_t*)W, nullptr, nullptr,
+                                                   nullptr, (bf16*)out, E, N, K, nblk);
   LIPA_CHECK_LAUNCH();
 }

@@ -25,6 +25,9 @@ over the codes:
 
     c13, s13, c2, s2 = quantize_experts(w13, w2)
     out = moe_experts_fp8(x, c13, s13, c2, s2, idx, w, base)
+
+and are differentiable in ``x``, ``w`` and ``base`` the same way, with two grouped launches over the codes as they are
+(``moe_gemm_dswiglu_fp8``, ``moe_gemm_dx_fp8``; ``moe_experts_fp8_backward_reference`` is their specification).
 """
 from __future__ import annotations
 
@@ -327,6 +330,48 @@ def moe_gemm_fp8_supported(x, c13, s13, c2, s2) -> bool:
     return ok and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (c13, s13, c2, s2))
 
 
+def _wq2(c2, s2):
+    """The dequantised down weights of the FP8 backward's first GEMM: bf16(fp32(val(c2))·s2), rounded to nearest even."""
+    return (c2.float() * s2.float()[..., None]).to(torch.bfloat16)
+
+
+def moe_experts_fp8_backward_reference(dout, x, c13, s13, c2, s2, idx, w):
+    """The per-pair specification of the backward of ``moe_experts_fp8`` (frozen FP8 experts), in torch: ``(dx, dw)``.
+
+    For each pair (t, j), e = idx[t, j], with g, u, h, y of ``moe_experts_fp8_reference`` (the scales meet the
+    unrounded sums):  gu = round(g), round(u) (what the forward saves);  dw[t, j] = Σ_h dout[t, h]·y[h];
+    dy = round(w[t, j]·dout[t]).  Both remaining scales run along the reduction index of their GEMM and cannot meet
+    an accumulator:
+    first GEMM:  wq2[e, h, i] = bf16(fp32(val(c2[e, h, i]))·s2[e, h]), one fp32 multiply rounded to nearest even, and
+    dh = dy·wq2[e] (fp32, never rounded).  This is the one place where a weight is rounded a second time;
+    dSwiGLU, with s = 1/(1 + exp(−g)) of the rounded g, folds the scale of ``c13`` in before its single rounding:
+    dgu'[n] = round(dh[n]·u·s·(1 + g·(1 − s))·s13[e, n]),  dgu'[I + n] = round(dh[n]·g·s·s13[e, I + n]);
+    second GEMM over the exact code values, no scale and no second rounding:  dxs = round(dgu'·val(c13[e]));
+    dx[t] = round(Σ_j dxs(t, j)) with the sum in fp32 in j order.  ``round`` is to x's dtype; fp64 ``x`` computes in
+    fp64 throughout (``wq2`` is a bf16 value whatever x's dtype).  dbase is dout."""
+    T, k = idx.shape
+    I = c2.shape[2]
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    wq2 = _wq2(c2, s2)
+    dx = torch.zeros(T, x.shape[1], dtype=acc, device=x.device)
+    dw = torch.zeros(T, k, dtype=acc, device=x.device)
+    for j in range(k):
+        e = idx[:, j]
+        c13e, s13e = c13[e].to(acc), s13[e].to(acc)
+        gu32 = torch.einsum("th,tnh->tn", x.to(acc), c13e) * s13e
+        h = (F.silu(gu32[:, :I]) * gu32[:, I:]).to(x.dtype)
+        y = (torch.einsum("ti,thi->th", h.to(acc), c2[e].to(acc)) * s2[e].to(acc)).to(x.dtype)
+        dw[:, j] = (dout.to(acc) * y.to(acc)).sum(-1)
+        gu = gu32.to(x.dtype).to(acc)
+        g, u = gu[:, :I], gu[:, I:]
+        dy = (w[:, j:j + 1].to(acc) * dout.to(acc)).to(x.dtype)
+        dh = torch.einsum("th,thi->ti", dy.to(acc), wq2[e].to(acc))
+        s = torch.sigmoid(g)
+        dgu = (torch.cat([dh * u * s * (1 + g * (1 - s)), dh * g * s], 1) * s13e).to(x.dtype)
+        dx = dx + torch.einsum("tn,tnh->th", dgu.to(acc), c13e).to(x.dtype).to(acc)
+    return dx.to(x.dtype), dw.to(w.dtype)
+
+
 def moe_gemm_swiglu_fp8(x, d: Dispatch, c13, s13, row_class: int = 0):
     """``moe_gemm_swiglu`` over e4m3 codes: the row scales meet the fp32 sums of g and u before SwiGLU."""
     return native().moe_gemm_swiglu_fp8(x.contiguous(), d.perm, d.offsets, c13, s13, d.k, row_class)
@@ -337,14 +382,38 @@ def moe_gemm_down_fp8(hs, d: Dispatch, c2, s2, row_class: int = 0):
     return native().moe_gemm_down_fp8(hs, d.offsets, c2, s2, row_class)
 
 
+class _ExpertsFp8Fn(torch.autograd.Function):
+    """``_ExpertsFn`` over the codes: x → ys through the two FP8 grouped launches.  Saves gu [P, 2I] (bf16), the codes
+    and scales and the dispatch; the backward is the two NN launches over the codes as they are and the combine."""
+
+    @staticmethod
+    def forward(ctx, x, c13, s13, c2, s2, pos_of, perm, offsets, k, row_class):
+        x = x.contiguous()
+        gu = torch.empty(perm.numel(), c13.shape[1], dtype=x.dtype, device=x.device)
+        hs = native().moe_gemm_swiglu_fp8(x, perm, offsets, c13, s13, k, row_class, gu)
+        ctx.save_for_backward(gu, c13, s13, c2, s2, pos_of, offsets)
+        ctx.k = k
+        return native().moe_gemm_down_fp8(hs, offsets, c2, s2, row_class)
+
+    @staticmethod
+    def backward(ctx, dys):
+        gu, c13, s13, c2, s2, pos_of, offsets = ctx.saved_tensors
+        dgu = native().moe_gemm_dswiglu_fp8(dys.contiguous(), gu, offsets, c2, s2, s13)
+        dxs = native().moe_gemm_dx_fp8(dgu, offsets, c13)
+        return (native().moe_combine(dxs, pos_of, ctx.k, None, None),) + (None,) * 9
+
+
 def moe_experts_fp8(x, c13, s13, c2, s2, idx, w, base=None, row_class: int = 0):
     """``moe_experts`` with weight-only FP8 experts (see ``moe_experts_fp8_reference``): dispatch, the two FP8
-    grouped launches and the unchanged combine, with no host read of the routing.  CPU tensors,
-    ``LIPA_REFERENCE=1``, unsupported shapes and inputs that require grad run the reference."""
-    grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, base))
-    if not use_native(x) or grad or not moe_gemm_fp8_supported(x, c13, s13, c2, s2) or idx.numel() == 0:
+    grouped launches and the unchanged combine, with no host read of the routing.  The same launches run under
+    autograd, bit-identical in the forward; the gradients of ``x``, ``w`` and ``base`` come from the grouped backward
+    over the codes (``moe_experts_fp8_backward_reference`` is their specification; the experts are frozen, codes have
+    no gradient).  CPU tensors, ``LIPA_REFERENCE=1``, unsupported shapes and ``idx.numel() == 0`` run the reference."""
+    if not use_native(x) or not moe_gemm_fp8_supported(x, c13, s13, c2, s2) or idx.numel() == 0:
         return moe_experts_fp8_reference(x, c13, s13, c2, s2, idx, w, base)
     d = moe_dispatch(idx, c13.shape[0])
-    hs = moe_gemm_swiglu_fp8(x, d, c13, s13, row_class)
-    ys = moe_gemm_down_fp8(hs, d, c2, s2, row_class)
+    if torch.is_grad_enabled() and x.requires_grad:
+        ys = fn_apply(_ExpertsFp8Fn, x, c13, s13, c2, s2, d.pos_of, d.perm, d.offsets, d.k, row_class)
+    else:           # nothing flows back through the GEMMs (w and base get theirs from the combine): no gu
+        ys = moe_gemm_down_fp8(moe_gemm_swiglu_fp8(x, d, c13, s13, row_class), d, c2, s2, row_class)
     return moe_combine(ys, d, w, base)

@@ -4,6 +4,7 @@ the segment offsets, two torch GEMMs and a SwiGLU per live expert, combine), one
 
     python scripts/bench_moe_gemm.py [--out profiles/r13/moe_gemm.txt]
     python scripts/bench_moe_gemm.py --backward [--out profiles/r15/moe_gemm_bwd.txt]   # training: see main_backward
+    python scripts/bench_moe_gemm.py --backward --fp8 [--out profiles/r16/moe_gemm_fp8_bwd.txt]   # main_backward_fp8
 
 Per T: device-event time of >= ITERS back-to-back calls (>= 50 ms) per round, ROUNDS rounds alternating the two;
 reported: the median of the round medians with min .. max.  Routing is uniform random; every call takes the next of
@@ -153,6 +154,77 @@ def main_backward(a):
     return lines
 
 
+def main_backward_fp8(a):
+    """``--backward --fp8``: forward + backward of ``moe_experts_fp8`` with ``x`` requiring grad (the FP8 grouped launches
+    and the two backward launches over the codes) against (a) autograd through ``moe_experts_fp8_reference``, the loop
+    that call ran before, and (b) the bf16 grouped forward + backward on the weights the codes came from, all three
+    interleaved round by round; ratios above 1 (FP8 grouped slower) are marked with ``**``.  Then the two backward
+    kernels over codes alone at T = 2048, beside their bf16 counterparts."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    w13 = (torch.randn(E, 2 * I, H, device=dev, generator=g) * H ** -0.5).bfloat16()
+    w2 = (torch.randn(E, H, I, device=dev, generator=g) * I ** -0.5).bfloat16()
+    q = moe.quantize_experts(w13, w2)
+    c13, s13, c2, s2 = q
+    lines = [f"routed expert MLP forward + backward (dx; frozen experts), E {E} top-{K} H {H} I {I}; {ROUNDS} rounds x >= "
+             f"{ITERS} calls (>= 50 ms), FP8 reference autograd loop / bf16 grouped / FP8 grouped interleaved, {NROUTE} "
+             f"uniform routings in turn",
+             f"{'T':>5} | {'fp8 reference loop us (min..max)':>36} | {'bf16 grouped us (min..max)':>32} | "
+             f"{'fp8 grouped us (min..max)':>32} | {'fp8/loop':>9} | {'fp8/bf16':>9}"]
+    for T in a.tokens:
+        x = torch.randn(T, H, device=dev, generator=g).bfloat16().requires_grad_()
+        dout = torch.randn(T, H, device=dev, generator=g).bfloat16()
+        routes = []
+        for _ in range(NROUTE):
+            idx = torch.rand(T, E, device=dev, generator=g).topk(K, -1).indices
+            routes.append((idx, torch.rand(T, K, device=dev, generator=g)))
+
+        def step(fn, wts, i):
+            return torch.autograd.grad(fn(x, *wts, *routes[i % NROUTE]), x, dout)[0]
+
+        fns = {"loop": lambda i: step(moe.moe_experts_fp8_reference, q, i),
+               "bf16": lambda i: step(moe.moe_experts, (w13, w2), i), "fp8": lambda i: step(moe.moe_experts_fp8, q, i)}
+        diff = (fns["loop"](0).float() - fns["fp8"](0).float()).abs().max().item()
+        for name, fn in fns.items():
+            for i in range(2 if name == "loop" else NROUTE):
+                fn(i)
+        torch.cuda.synchronize()
+        iters = max(ITERS, min(1000, int(5e4 / timed(fns["bf16"], ITERS))))
+        t = {n: [] for n in fns}
+        for _ in range(ROUNDS):
+            for name, fn in fns.items():
+                t[name].append(timed(fn, ITERS if name == "loop" else iters))
+        med = {n: statistics.median(v) for n, v in t.items()}
+        cell = {n: f"{med[n]:9.1f} ({min(t[n]):.1f}..{max(t[n]):.1f})" for n in t}
+        r = [("**%.3f**" if med["fp8"] > med[n] else "%.3f") % (med["fp8"] / med[n]) for n in ("loop", "bf16")]
+        lines.append(f"{T:>5} | {cell['loop']:>36} | {cell['bf16']:>32} | {cell['fp8']:>32} | {r[0]:>9} | {r[1]:>9}"
+                     f"   (max |dx loop - dx fp8 grouped| {diff:.2e})")
+        print(lines[-1], flush=True)
+    T, P = 2048, 2048 * K
+    ds = [moe.moe_dispatch(torch.rand(T, E, device=dev, generator=g).topk(K, -1).indices, E) for _ in range(NROUTE)]
+    dys = torch.randn(P, H, device=dev, generator=g).bfloat16()
+    gu = torch.randn(P, 2 * I, device=dev, generator=g).bfloat16()
+    dgu = native().moe_gemm_dswiglu(dys, gu, ds[0].offsets, w2)
+    C = native()
+    kern = {"moe_gemm_nn_k<dswiglu>": (lambda i: C.moe_gemm_dswiglu(dys, gu, ds[i % NROUTE].offsets, w2), 2 * P * H * I),
+            "moe_gemm_nn_fp8_k<dswiglu>": (lambda i: C.moe_gemm_dswiglu_fp8(dys, gu, ds[i % NROUTE].offsets, c2, s2, s13),
+                                           2 * P * H * I),
+            "moe_gemm_nn_k<dx>": (lambda i: C.moe_gemm_dx(dgu, ds[i % NROUTE].offsets, w13), 4 * P * H * I),
+            "moe_gemm_nn_fp8_k<dx>": (lambda i: C.moe_gemm_dx_fp8(dgu, ds[i % NROUTE].offsets, c13), 4 * P * H * I)}
+    lines.append(f"backward kernels alone, T {T} (P {P}), {ROUNDS} rounds x 200 launches each, interleaved, median (min..max)")
+    for fn, _ in kern.values():
+        timed(fn, NROUTE)
+    v = {n: [] for n in kern}
+    for _ in range(ROUNDS):
+        for name, (fn, _) in kern.items():
+            v[name].append(timed(fn, 200))
+    for name, (_, flop) in kern.items():
+        med = statistics.median(v[name])
+        lines.append(f"{name:>28} | {med:8.1f} us ({min(v[name]):.1f}..{max(v[name]):.1f}) | {flop / med / 1e9:.3f} PFLOP/s")
+        print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -164,7 +236,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe_gemm: needs the GPU (no CPU fall-back for a timing)")
     if a.fp8 or a.backward:
-        text = "\n".join(main_backward(a) if a.backward else main_fp8(a)) + "\n"
+        text = "\n".join((main_backward_fp8 if a.fp8 else main_backward)(a) if a.backward else main_fp8(a)) + "\n"
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
